@@ -9,11 +9,16 @@ A "step" is one pass of the hot path (`CAVP.forward`) over one b
 (SURVEY.md §8e): every rank runs the same per-GPU batch (weak scaling) and the inference path needs no collective;
 `value` = N * B * K / max-over-ranks(elapsed).
 
-Extra objects on the JSON line:
-  roofline     — the dominant kernel (MFMA implicit-GEMM conv/linear): algorithmic FLOPs / bytes of all its launches in
-                 one step ÷ their summed duration, measured live with HIP events on the launching stream.
-  cpu_baseline — the CPU oracle (pure-PyTorch restatement pinned to the reference by tests/golden) timed on this box's
-                 host cores on a bounded sample of the same workload (rank 0, N=1 only).
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when --dump-outputs DIR is
+given and prints the line.  With --full the line also carries the secondary measurements, each taken after the timed
+region (the --no-* switches below drop single ones):
+  roofline        — the dominant kernel (MFMA implicit-GEMM conv/linear): algorithmic FLOPs / bytes of all its launches in
+                    one step ÷ their summed duration, measured live with HIP events on the launching stream.
+  eval_forward    — the inference forward of the same model on one hipGraph (default training line only).
+  f32_parity_path — the same training step on the f32 kernels (c1p / c1, bf16 training line only).
+  cpu_baseline    — the CPU oracle (pure-PyTorch restatement pinned to the reference by tests/golden) timed on this box's
+                    host cores on a bounded sample of the same workload (rank 0, N=1 only).
+  collective      — the two gradient all-reduce pieces timed alone (N > 1 training only).
 """
 from __future__ import annotations
 
@@ -38,6 +43,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the secondary measurements (roofline, eval_forward, f32_parity_path, "
+                         "cpu_baseline, collective); a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step handed its caller to DIR/<name>.npy (float32 / float64, <= 64 MB in all): "
+                         "loss + parameter gradients (training), the returned tensors (inference)")
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU per step")
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--mode", choices=["train", "eval"], default="train",
@@ -690,10 +701,57 @@ def self_launch(a) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 2 << 20    # an array with more elements is written as this many of them, at fixed seeded positions
+
+
+def dump_outputs(out_dir, result, model, train):
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name>.npy in float32 / float64, so that two
+    builds can be compared output for output on identical inputs.  Training step: `loss`, `grad_sample` (the parameter gradients
+    concatenated in named_parameters() order, a parameter without a gradient as zeros) and `grad_norms` (float64 L2 norm of each
+    gradient, same order).  Inference: every tensor the forward returned (`logits`, `fusion`, `pack_<key>`)."""
+    import zlib
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {}
+    if train:
+        ps = [p for _, p in model.named_parameters()]
+        arrays["loss"] = result.detach().reshape(-1)
+        arrays["grad_sample"] = torch.cat([p.grad.detach().float().reshape(-1) if p.grad is not None
+                                           else torch.zeros(p.numel(), dtype=torch.float32, device=p.device) for p in ps])
+        arrays["grad_norms"] = torch.stack([torch.linalg.vector_norm(p.grad.detach(), dtype=torch.float64) if p.grad is not None
+                                            else torch.zeros((), dtype=torch.float64, device=p.device) for p in ps])
+    else:
+        out, fusion, pack = result
+        arrays["logits"], arrays["fusion"] = out, fusion
+        for k in sorted(pack):
+            if isinstance(pack[k], torch.Tensor):
+                arrays["pack_" + k] = pack[k]
+    total = 0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        v = t.cpu().numpy()
+        total += v.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a))
+    a.full = a.full or a.pmc or a.cpu_protocol_full   # (both only refine a secondary measurement)
+    if not a.full:   # a plain run: the headline only
+        a.no_roofline = a.no_eval_leg = a.no_f32 = a.no_cpu_baseline = True
+    # identical inputs from run to run: the weights and batches are seeded (cavp_amd/synth.py); this seeds the host draws of the
+    # steps themselves (ContrastLoss sampling of c5, PVT DropPath of c4)
+    torch.manual_seed(0)
     cap_host_threads()
     if a.lib:
         from cavp_amd import _lib as _cl9
@@ -849,7 +907,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            step()
+            result = step()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -859,8 +917,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, result, model, train)
     collective = None
-    if world > 1 and train and getattr(model, "_grad_arena", None) is not None:
+    if a.full and world > 1 and train and getattr(model, "_grad_arena", None) is not None:
         # the two gradient collectives of a step on their own (nothing else on the device), max over ranks: what the step would
         # pay if nothing overlapped - the timed region above hides the early piece behind the backbone's backward
         from cavp_amd.train import _allreduce_range, grad_allreduce_dtype
@@ -946,7 +1006,7 @@ def main():
                     "measured_vs_fused_min": round(meas_bytes / 1e9 / min_gb, 2) if meas_bytes else None,
                 }
             line["roofline"] = roof
-        if getattr(a, "trainer_graphed", False) and a.dtype == "bf16":
+        if a.full and getattr(a, "trainer_graphed", False) and a.dtype == "bf16":
             # (--trainer-loop / c5 on graph replays: no per-launch view, but the whole step against both roofs: the algorithmic
             # FLOPs of the same model's fused eager step, counted once through the launch wrappers, and the fused byte minimum)
             try:

@@ -27,8 +27,8 @@ def test_two_rank_bench_on_one_gpu(mode, launcher, wire):
     env = dict(os.environ, CAVP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--mode", mode, "--grad-allreduce", wire]
-    if launcher == "torchrun":   # as the driver runs N > 1; default flags: the roofline leg must stay rank-local
+    args = ["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--mode", mode, "--grad-allreduce", wire]
+    if launcher == "torchrun":   # as the driver runs N > 1; --full: the roofline leg must stay rank-local
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.join(REPO, "bench.py")] + args
     else:                        # plain `python bench.py --gpus 2`: bench.py starts its own two ranks (main_vpo_mono.py:274-275)

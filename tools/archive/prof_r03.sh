@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 T=${1:-end}
 O=gpurun_out/r03
 mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench_train_bf16_$T.json 2> $O/bench_train_$T.err
-CAVP_BENCH_PER_LAYER=$O/layers_train_bf16_$T.txt python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-f32 > /dev/null 2>&1
+python bench.py --full --steps 20 --warmup 5 > $O/bench_train_bf16_$T.json 2> $O/bench_train_$T.err
+CAVP_BENCH_PER_LAYER=$O/layers_train_bf16_$T.txt python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-f32 > /dev/null 2>&1
 rm -rf $O/prof_train_$T
 (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_train_$T -o train -- \
    python $GRAFT_REPO_ROOT/bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-f32 > $GRAFT_REPO_ROOT/$O/prof_train_$T.log 2>&1)
