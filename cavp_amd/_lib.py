@@ -13,9 +13,9 @@ import torch  # noqa: F401  (ordering dependency, see above)
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcavp_hip.so")
 
-F32, BF16 = 0, 1
+F32, BF16, I64 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_GELU = 0, 1, 2, 3
-ABI_VERSION = 12
+ABI_VERSION = 13
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH = -1, -2, -3, -4, -5   # cavp_status_t
 WGRAD_GROUP_MAX = 16   # CAVP_WGRAD_GROUP_MAX
 
@@ -145,6 +145,10 @@ PROTOTYPES = {
     "cavp_smallcin_kxk_im2col": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_space_to_depth": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_row_scale_add": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
+    # ---- validation metrics ----
+    "cavp_seg_confusion_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp]),
+    "cavp_mask_iou_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp]),
+    "cavp_fmeasure_hist": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,287 @@
+// Validation metrics for gfx950: the integer counts behind the reference's MIoU / ForegroundDetect (utils/eval_utils.py) and
+// mask_iou / Eval_Fmeasure (utils/avsbench_utils.py).  Every kernel streams its input once and accumulates integer counts with
+// integer atomics, so a result does not depend on the order in which workgroups arrive: bit-reproducible without
+// cavp_set_deterministic.  The float finalisation (IoU, F-beta, precision / recall curves) stays in cavp_amd/metrics.py, in the
+// reference's own expressions.
+//
+//   seg_confusion: argmax over C per pixel (first maximal index, a NaN counts as the maximum: torch.max), then one count in the
+//                  (K+1) x K matrix M[row(t)][p] for every pixel whose label t >= 0 and t != ignore; row(t) = t < K ? t : K.
+//                  Privatised per workgroup as u32 in LDS when (K+1)*K*4 <= 64 KiB (K <= 127), flushed with one u64 atomic per
+//                  non-zero bin; larger K adds straight into M.  The background-correct bin takes most pixels: equal bins are
+//                  merged inside a thread's 4 pixels, and the first bin of the wave is summed across the wave (three ballots)
+//                  before its one atomic.
+//   mask_iou_stats: per image  sum p*t, sum max(p, t), sum (1-t)(1-p), sum t  in int64.
+//   fmeasure_hist:  per image a (pr_num+1)-bin histogram of bin(p) = #{i : th[i] <= p} over all pixels and over gt != 0;
+//                  suffix sums of it are Eval_Fmeasure's y_temp.sum() and tp for every threshold.
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kLdsBins = 16384;   // 64 KiB of u32 counts
+
+__device__ __forceinline__ void argmax_step(float v, int c, float& best, int& idx) {
+  if (v > best || (v != v && best == best)) { best = v; idx = c; }
+}
+
+// Add the (bin, count) pairs of one thread's 4 pixels (bin < 0: nothing).  Wave-uniform call.
+template <bool kLds>
+__device__ __forceinline__ void add_bins(int b[4], unsigned* lds, unsigned long long* gM) {
+  int cnt[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cnt[i] = b[i] >= 0 ? 1 : 0;
+#pragma unroll
+  for (int i = 1; i < 4; ++i) {
+#pragma unroll
+    for (int j = 0; j < i; ++j) {
+      if (b[i] >= 0 && b[j] == b[i]) { cnt[j] += cnt[i]; cnt[i] = 0; b[i] = -1; }
+    }
+  }
+  // the wave's first bin (in practice the hot background-correct one): one atomic for the whole wave
+  const int first = b[0] >= 0 ? b[0] : (b[1] >= 0 ? b[1] : (b[2] >= 0 ? b[2] : b[3]));
+  const unsigned long long any = __ballot(first >= 0);
+  if (any) {
+    const int lead = __shfl(first, __ffsll((long long)any) - 1, 64);
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (b[i] == lead) { c = cnt[i]; b[i] = -1; }
+    }
+    const unsigned total = (unsigned)__popcll(__ballot(c & 1)) + 2u * (unsigned)__popcll(__ballot(c & 2)) +
+                           4u * (unsigned)__popcll(__ballot(c & 4));
+    if ((threadIdx.x & 63) == 0) {
+      if (kLds) atomicAdd(lds + lead, total);
+      else atomicAdd(gM + lead, (unsigned long long)total);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (b[i] >= 0) {
+      if (kLds) atomicAdd(lds + b[i], (unsigned)cnt[i]);
+      else atomicAdd(gM + b[i], (unsigned long long)cnt[i]);
+    }
+  }
+}
+
+// labels are int64, or float32 holding integers (AVS masks come as float); a non-finite float label is never counted
+__device__ __forceinline__ long long label_i64(long long t) { return t; }
+__device__ __forceinline__ long long label_i64(float t) { return fabsf(t) <= 9.0e18f ? (long long)t : -1; }
+
+template <typename LT>
+__device__ __forceinline__ int conf_bin(LT tv, int p, int K, long long ignore) {
+  const long long t = label_i64(tv);
+  if (t < 0 || t == ignore) return -1;
+  const int row = t < K ? (int)t : K;
+  return row * K + p;
+}
+
+// One thread = 4 consecutive pixels of one image ("quad"); the grid strides over all N * ceil(HW/4) quads with a block-uniform trip
+// count, so every wave reaches the ballots of add_bins with all lanes.
+template <bool kVec, bool kLds, typename LT>
+__global__ __launch_bounds__(kThreads) void seg_confusion_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
+                                                                int N, int C, long long HW, int K, long long ignore,
+                                                                unsigned long long* __restrict__ M) {
+  extern __shared__ unsigned hist[];
+  const int nbins = (K + 1) * K;
+  if (kLds) {
+    for (int i = threadIdx.x; i < nbins; i += kThreads) hist[i] = 0u;
+    __syncthreads();
+  }
+  const long long nq = (HW + 3) >> 2, total = (long long)N * nq;
+  for (long long base = (long long)blockIdx.x * kThreads; base < total; base += (long long)gridDim.x * kThreads) {
+    const long long q = base + threadIdx.x;
+    int b[4] = {-1, -1, -1, -1};
+    if (q < total) {
+      const long long n = q / nq, p0 = (q - n * nq) * 4;
+      const float* src = logits + n * C * HW + p0;
+      const LT* lab = labels + n * HW + p0;
+      if (kVec) {
+        float4 best = *(const float4*)src;
+        int i0 = 0, i1 = 0, i2 = 0, i3 = 0;
+        for (int c = 1; c < C; ++c) {
+          const float4 v = *(const float4*)(src + c * HW);
+          argmax_step(v.x, c, best.x, i0);
+          argmax_step(v.y, c, best.y, i1);
+          argmax_step(v.z, c, best.z, i2);
+          argmax_step(v.w, c, best.w, i3);
+        }
+        LT t[4];
+        if constexpr (sizeof(LT) == 8) {
+          const longlong2 t01 = *(const longlong2*)lab, t23 = *(const longlong2*)(lab + 2);
+          t[0] = t01.x; t[1] = t01.y; t[2] = t23.x; t[3] = t23.y;
+        } else {
+          const float4 t4 = *(const float4*)lab;
+          t[0] = t4.x; t[1] = t4.y; t[2] = t4.z; t[3] = t4.w;
+        }
+        b[0] = conf_bin(t[0], i0, K, ignore);
+        b[1] = conf_bin(t[1], i1, K, ignore);
+        b[2] = conf_bin(t[2], i2, K, ignore);
+        b[3] = conf_bin(t[3], i3, K, ignore);
+      } else {
+        const int np = (int)(HW - p0 < 4 ? HW - p0 : 4);
+        float best[4];
+        int idx[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) best[j] = j < np ? src[j] : 0.f;
+        for (int c = 1; c < C; ++c) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (j < np) argmax_step(src[c * HW + j], c, best[j], idx[j]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(lab[j], idx[j], K, ignore) : -1;
+      }
+    }
+    add_bins<kLds>(b, hist, M);
+  }
+  if (kLds) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nbins; i += kThreads) {
+      const unsigned v = hist[i];
+      if (v) atomicAdd(M + i, (unsigned long long)v);
+    }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ long long as_i64(const T* p, long long i) { return (long long)p[i]; }
+
+template <typename TP, typename TT>
+__global__ __launch_bounds__(kThreads) void mask_iou_stats_kernel(const TP* __restrict__ pred, const TT* __restrict__ target,
+                                                                 long long HW, unsigned long long* __restrict__ out) {
+  const long long n = blockIdx.y;
+  const TP* P = pred + n * HW;
+  const TT* T = target + n * HW;
+  long long s[4] = {0, 0, 0, 0};
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < HW; i += (long long)gridDim.x * kThreads) {
+    const long long p = as_i64(P, i), t = as_i64(T, i);
+    s[0] += p * t;
+    s[1] += p > t ? p : t;
+    s[2] += (1 - t) * (1 - p);
+    s[3] += t;
+  }
+  __shared__ long long part[kThreads / 64][4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    long long v = s[k];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    long long v = 0;
+    for (int w = 0; w < kThreads / 64; ++w) v += part[w][threadIdx.x];
+    atomicAdd(out + n * 4 + threadIdx.x, (unsigned long long)v);   // two's complement: a signed sum
+  }
+}
+
+template <typename TG>
+__global__ __launch_bounds__(kThreads) void fmeasure_hist_kernel(const float* __restrict__ src, long long src_ld, const TG* __restrict__ gt,
+                                                                const float* __restrict__ th, int C, int channel, long long HW,
+                                                                int pr_num, unsigned* __restrict__ hist) {
+  extern __shared__ unsigned smem[];
+  float* s_th = (float*)smem;
+  unsigned* h0 = smem + pr_num;
+  unsigned* h1 = h0 + pr_num + 1;
+  for (int i = threadIdx.x; i < pr_num; i += kThreads) s_th[i] = th[i];
+  for (int i = threadIdx.x; i < 2 * (pr_num + 1); i += kThreads) h0[i] = 0u;
+  __syncthreads();
+  const long long n = blockIdx.y;
+  const TG* G = gt + n * HW;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < HW; i += (long long)gridDim.x * kThreads) {
+    float p;
+    if (C == 0) {
+      p = src[n * src_ld + i];
+    } else {   // softmax over C, channel `channel` (trainer_cavp_avs_obj.py:343 torch.softmax(vid_pred, 1)[:, 1])
+      const float* x = src + n * src_ld + i;
+      float m = x[0];
+      for (int c = 1; c < C; ++c) m = fmaxf(m, x[c * HW]);
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += expf(x[c * HW] - m);
+      p = expf(x[channel * HW] - m) / s;
+    }
+    int lo = 0, hi = pr_num;   // #{i : th[i] <= p} on the ascending table (a NaN lands in bin 0: p >= th is false for all)
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_th[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    atomicAdd(h0 + lo, 1u);
+    if (G[i] != (TG)0) atomicAdd(h1 + lo, 1u);
+  }
+  __syncthreads();
+  unsigned* out = hist + n * 2 * (pr_num + 1);
+  for (int i = threadIdx.x; i < 2 * (pr_num + 1); i += kThreads) {
+    const unsigned v = h0[i];
+    if (v) atomicAdd(out + i, v);
+  }
+}
+
+int chunks_for(long long work, long long per_block, int cap) {
+  long long c = (work + per_block - 1) / per_block;
+  return (int)(c < 1 ? 1 : (c > cap ? cap : c));
+}
+
+}  // namespace
+
+template <typename LT>
+void launch_confusion(bool vec, bool lds, int grid, size_t shm, hipStream_t s, const float* logits, const LT* lab, int N, int C,
+                      long long HW, int K, long long ignore, unsigned long long* m) {
+  if (vec && lds) seg_confusion_kernel<true, true, LT><<<grid, kThreads, shm, s>>>(logits, lab, N, C, HW, K, ignore, m);
+  else if (vec) seg_confusion_kernel<true, false, LT><<<grid, kThreads, 0, s>>>(logits, lab, N, C, HW, K, ignore, m);
+  else if (lds) seg_confusion_kernel<false, true, LT><<<grid, kThreads, shm, s>>>(logits, lab, N, C, HW, K, ignore, m);
+  else seg_confusion_kernel<false, false, LT><<<grid, kThreads, 0, s>>>(logits, lab, N, C, HW, K, ignore, m);
+}
+
+extern "C" int cavp_seg_confusion_nchw(const float* logits, const void* labels, int32_t label_dtype, int32_t N, int32_t C, int64_t HW,
+                                       int32_t K, int64_t ignore, uint64_t* M, void* stream) {
+  if (!logits || !labels || !M || N <= 0 || C <= 0 || HW <= 0 || K <= 0) return CAVP_ERR_BAD_ARG;
+  if (K < C || K > CAVP_METRICS_MAX_CLASSES) return CAVP_ERR_UNSUPPORTED;
+  const bool li = label_dtype == CAVP_I64;
+  if (!li && label_dtype != CAVP_F32) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)labels & (li ? 7 : 3)) || ((uintptr_t)M & 7) || ((uintptr_t)logits & 3)) return CAVP_ERR_ALIGN;
+  const bool vec = (HW & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)labels & 15) == 0;
+  const bool lds = (K + 1) * K <= kLdsBins;
+  const long long quads = (long long)N * ((HW + 3) >> 2);
+  // one quad per thread for B=32 at 224^2 (1568 workgroups, all resident); each workgroup flushes its non-zero LDS bins once
+  const int grid = chunks_for(quads, kThreads, lds ? 2048 : 4096);
+  const size_t shm = lds ? (size_t)(K + 1) * K * sizeof(unsigned) : 0;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* m = (unsigned long long*)M;
+  if (li) launch_confusion(vec, lds, grid, shm, s, logits, (const long long*)labels, N, C, HW, K, ignore, m);
+  else launch_confusion(vec, lds, grid, shm, s, logits, (const float*)labels, N, C, HW, K, ignore, m);
+  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+}
+
+extern "C" int cavp_mask_iou_stats(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t N,
+                                   int64_t HW, int64_t* out, void* stream) {
+  if (!pred || !target || !out || N <= 0 || HW <= 0) return CAVP_ERR_BAD_ARG;
+  const bool pi = pred_dtype == CAVP_I64, ti = target_dtype == CAVP_I64;
+  if ((!pi && pred_dtype != CAVP_F32) || (!ti && target_dtype != CAVP_F32)) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)pred & (pi ? 7 : 3)) || ((uintptr_t)target & (ti ? 7 : 3)) || ((uintptr_t)out & 7)) return CAVP_ERR_ALIGN;
+  const dim3 grid(chunks_for(HW, 4 * kThreads, 256), N);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* o = (unsigned long long*)out;
+  if (pi && ti) mask_iou_stats_kernel<long long, long long><<<grid, kThreads, 0, s>>>((const long long*)pred, (const long long*)target, HW, o);
+  else if (pi) mask_iou_stats_kernel<long long, float><<<grid, kThreads, 0, s>>>((const long long*)pred, (const float*)target, HW, o);
+  else if (ti) mask_iou_stats_kernel<float, long long><<<grid, kThreads, 0, s>>>((const float*)pred, (const long long*)target, HW, o);
+  else mask_iou_stats_kernel<float, float><<<grid, kThreads, 0, s>>>((const float*)pred, (const float*)target, HW, o);
+  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+}
+
+extern "C" int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, const void* gt, int32_t gt_dtype, const float* thresholds, int32_t N, int32_t C,
+                                  int32_t channel, int64_t HW, int32_t pr_num, uint32_t* hist, void* stream) {
+  if (!src || !gt || !thresholds || !hist || N <= 0 || HW <= 0 || pr_num <= 0 || C < 0 || C == 1) return CAVP_ERR_BAD_ARG;
+  if (C >= 2 && (channel < 0 || channel >= C)) return CAVP_ERR_BAD_ARG;
+  if (src_image_stride < (C >= 2 ? (int64_t)C * HW : HW) && N > 1) return CAVP_ERR_BAD_ARG;
+  if (pr_num > CAVP_FMEASURE_MAX_THRESHOLDS) return CAVP_ERR_UNSUPPORTED;
+  const bool gi = gt_dtype == CAVP_I64;
+  if (!gi && gt_dtype != CAVP_F32) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)src & 3) || ((uintptr_t)gt & (gi ? 7 : 3)) || ((uintptr_t)thresholds & 3) || ((uintptr_t)hist & 3)) return CAVP_ERR_ALIGN;
+  const dim3 grid(chunks_for(HW, 4 * kThreads, 256), N);
+  const size_t shm = (size_t)(pr_num + 2 * (pr_num + 1)) * sizeof(unsigned);
+  hipStream_t s = (hipStream_t)stream;
+  if (gi) fmeasure_hist_kernel<long long><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const long long*)gt, thresholds, C, channel, HW, pr_num, hist);
+  else fmeasure_hist_kernel<float><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const float*)gt, thresholds, C, channel, HW, pr_num, hist);
+  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+}

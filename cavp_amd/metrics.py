@@ -1,0 +1,244 @@
+"""Validation metrics on the GPU, under the reference's names (utils/eval_utils.py: MIoU, ForegroundDetect, get_performance;
+utils/avsbench_utils.py: mask_iou, Eval_Fmeasure).
+
+The counting runs in libcavp_hip.so (cavp_seg_confusion_nchw, cavp_mask_iou_stats, cavp_fmeasure_hist): one pass over the
+logits / masks, exact integer counts.  What the reference computes in floating point from those counts (IoU, accuracy, FDR,
+F-beta, the precision / recall curves) is done here in the reference's dtypes and operation order, so the results equal the
+reference's as long as its own float32 accumulators are exact: MIoU's per-class sums stay below 2^24 pixels (a few hundred
+224^2 frames for the largest class).  Beyond that the reference's float32 sums round; the int64 counts here do not.
+
+    from cavp_amd.metrics import MIoU, ForegroundDetect, get_performance, mask_iou, Eval_Fmeasure
+
+Differences from the reference, on purpose:
+  * the target is never written to (MIoU.__call__ of the reference stores -1 into the caller's ignore pixels);
+  * targets must be [B, H, W] with B, H, W of the logits [B, C, H, W], int64 or float32 holding integers (AVS masks);
+    anything else raises CavpError;
+  * MIoU.inter / .union / .correct / .label are exact int64 counts (float32 arrays in the reference);
+  * Eval_Fmeasure treats gt as a binary mask (gt != 0), as the AVS trainers feed it;
+  * mask_iou's float inputs must be masks (integer values): each pixel is truncated to an integer before summing;
+  * device tensors only: there is no CPU path (CavpError).
+Additions: `update(x, y)` (no host sync; no allocation after the first call, so it can be captured in a hipGraph with the eval
+forward), `reset()`, `counts()` (the device-side (K+1) x K confusion counts) and `fmeasure_curve(...)` (the score curve as a
+device tensor, without `.item()`)."""
+from __future__ import annotations
+
+import numpy
+import torch
+
+from . import ops
+from ._lib import CavpError
+from .train_ops import zero_ as _zero_
+from .train_ops import zeros as _zeros
+
+__all__ = ["MIoU", "ForegroundDetect", "get_performance", "mask_iou", "Eval_Fmeasure", "fmeasure_curve"]
+
+
+def get_performance(miou_measure_in, fg_measure_in, class_list=None):
+    """(mIoU, acc, FDR, F1, F0.3) of the two accumulators."""
+    return (*miou_measure_in.get_metric_results(class_list), *fg_measure_in.get_metric_results(class_list))
+
+
+def iou_and_accuracy(M: numpy.ndarray):
+    """Per-class IoU (float64 [K]) and pixel accuracy (float64) from the (K+1) x K counts M: intersection = diagonal, union =
+    predicted + labelled - intersection (row K holds valid labels >= K, predicted but never labelled as a class), accuracy =
+    trace / all counted pixels, each over (spacing(1) + denominator) in float64."""
+    k = M.shape[1]
+    hits = numpy.diag(M[:k]).astype(numpy.int64)
+    union = M.sum(0) + M[:k].sum(1) - hits
+    eps = numpy.spacing(1)
+    return hits, union, hits.astype(numpy.float64) / (union + eps), float(numpy.trace(M[:k])) / (M.sum() + eps)
+
+
+def detection_scores(cm: torch.Tensor, class_list=None):
+    """(FDR, F1, F0.3) of a float64 K x K confusion matrix (rows: label, columns: prediction), nan-means over the classes
+    (or over `class_list`), each rounded to 4 decimals as a 0-d numpy array."""
+    hits = torch.diag(cm)
+    false_pos = cm.sum(dim=0) - hits
+    missed = cm.sum(dim=1) - hits
+    if class_list is not None:
+        hits, false_pos, missed = hits[class_list], false_pos[class_list], missed[class_list]
+
+    def f_beta(b2):
+        weighted = (1 + b2) * hits
+        return torch.nanmean(weighted / (weighted + b2 * missed + false_pos))
+
+    scores = (torch.nanmean(false_pos / (false_pos + hits)), f_beta(1.0), f_beta(0.3))
+    return tuple(torch.round(v, decimals=4).cpu().numpy() for v in scores)
+
+
+class _Confusion:
+    """(K+1) x K int64 counts on the device: M[t][p] for labels t < K, M[K][p] for valid labels >= K (cavp_seg_confusion_nchw)."""
+
+    def _init_counts(self, num_classes: int, ignore):
+        self.num_classes = int(num_classes)
+        self._kernel_ignore = -1 if ignore is None else int(ignore)   # -1 is never a valid label (t >= 0)
+        self._M = None
+
+    def update(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        """Accumulate one batch: x logits [B, C, H, W] (float32), y labels [B, H, W] (int64, or float32 holding integers).
+        No host sync; graph replays of a captured update() accumulate the same way."""
+        if x.dim() != 4 or y.dim() != 3 or y.shape[0] != x.shape[0] or tuple(y.shape[1:]) != tuple(x.shape[2:]):
+            raise CavpError(f"{type(self).__name__}: logits [B, C, H, W] and target [B, H, W] required, got "
+                            f"{tuple(x.shape)} / {tuple(y.shape)}")
+        ops._need_gpu(x, y)
+        k = self.num_classes
+        if self._M is None or self._M.device != x.device:
+            self._M = _zeros(((k + 1) * k,), torch.int64, x.device)
+        ops.seg_confusion(x.detach(), y, k, self._kernel_ignore, self._M)
+
+    def counts(self) -> torch.Tensor:
+        """The (K+1) x K confusion counts (int64, on the device; zeros on the CPU before the first update)."""
+        k = self.num_classes
+        if self._M is None:
+            return torch.zeros((k + 1, k), dtype=torch.int64)
+        return self._M.view(k + 1, k)
+
+    def reset(self) -> None:
+        if self._M is not None:
+            _zero_(self._M)
+
+    def _host_counts(self) -> numpy.ndarray:
+        return self.counts().cpu().numpy()
+
+
+class MIoU(_Confusion):
+    """Mean IoU and pixel accuracy over all batches seen (labels == ignore_index and negative labels are not counted)."""
+
+    def __init__(self, num_classes, ignore_index, local_rank):
+        self.ignore_index = ignore_index
+        self.local_rank = local_rank
+        self._init_counts(num_classes, ignore_index)
+        self._refresh()
+
+    def _refresh(self):
+        """inter / union / correct / label, iou and acc from the current device counts (one host copy); the constructor's zeros
+        before the first update.  Always read afresh: graph replays and reset() change the counts behind Python's back."""
+        if self._M is None:
+            self.inter, self.union, self.correct, self.label = 0, 0, 0, 0
+            self.iou, self.acc = numpy.zeros(self.num_classes, dtype=numpy.int64), 0.0
+            return
+        M = self._host_counts()
+        self.inter, self.union, self.iou, self.acc = iou_and_accuracy(M)
+        self.correct, self.label = int(numpy.trace(M[: self.num_classes])), int(M.sum())
+
+    def get_metric_results(self, class_list=None):
+        """(mIoU, acc) rounded to 4 decimals; mIoU over `class_list` when given."""
+        self._refresh()
+        iou = self.iou if class_list is None else self.iou[class_list]
+        return numpy.round(iou.mean().item(), 4), numpy.round(self.acc, 4)
+
+    def __call__(self, x, y):
+        self.update(x, y)
+        return self.get_metric_results()
+
+
+class ForegroundDetect(_Confusion):
+    """Per-class false discovery rate and F-scores from the label x prediction confusion matrix over all batches seen."""
+
+    def __init__(self, num_classes, ignore_class=255, local_rank=0):
+        self.ignore = ignore_class
+        self.local_rank = local_rank
+        self._init_counts(num_classes, ignore_class)
+
+    @property
+    def confusion_matrix_(self) -> numpy.ndarray:
+        """The reference's float64 K x K matrix (rows: label, columns: prediction); a host copy of the device counts."""
+        return self._host_counts()[: self.num_classes].astype(numpy.float64)
+
+    def get_metric_results(self, class_list=None):
+        """(FDR, F1, F0.3) rounded to 4 decimals (0-d numpy arrays); over `class_list` when given."""
+        return detection_scores(torch.tensor(self.confusion_matrix_), class_list)
+
+    def __call__(self, y_hat, y):
+        self.update(y_hat, y)
+
+
+def mask_iou_from_stats(stats: torch.Tensor, num_pixels: int, dtype: torch.dtype, eps: float = 1e-7) -> torch.Tensor:
+    """mask_iou's tail from the per-image sums stats[N, 4] = (sum p*t, sum max(p, t), sum (1-t)(1-p), sum t) in `dtype`, the dtype
+    of the reference's sums (torch.result_type(pred, target)): a frame with an empty target scores its background overlap over
+    all pixels; the mean over frames of overlap / (union + eps)."""
+    if dtype != torch.int64:
+        stats = stats.to(dtype)
+    overlap, union, bg_overlap, t_sum = stats.unbind(1)
+    empty = t_sum == 0
+    overlap = torch.where(empty, bg_overlap, overlap)
+    union = union.masked_fill(empty, num_pixels)
+    return torch.sum(overlap / (union + eps)) / stats.shape[0]
+
+
+def mask_iou(pred, target, eps=1e-7, size_average=True):
+    """Mean IoU of binary masks pred / target [N, H, W] (int64 or float32) as a 0-d device tensor; size_average is accepted and
+    unused.  Float inputs must hold integers: each pixel is truncated to an integer before summing, so a probability map gives a
+    different answer from the reference, which sums the floats."""
+    if len(pred.shape) != 3 or pred.shape != target.shape:
+        raise CavpError(f"mask_iou: pred and target must be [N, H, W] of one shape, got {tuple(pred.shape)} / {tuple(target.shape)}")
+    ops._need_gpu(pred, target)
+    n = pred.size(0)
+    stats = ops.mask_iou_stats(pred, target, _zeros((n, 4), torch.int64, pred.device))
+    return mask_iou_from_stats(stats, pred.size(-1) * pred.size(-2), torch.result_type(pred, target), eps)
+
+
+_thresholds = {}
+
+
+def thresholds(pr_num: int, device) -> torch.Tensor:
+    """_eval_pr's threshold table: torch.linspace(0, 1 - 1e-10, pr_num) built on the CPU and moved to the device, as the reference
+    does (cached; the histogram kernel needs it ascending, checked once)."""
+    key = (torch.device(device), int(pr_num))
+    th = _thresholds.get(key)
+    if th is None:
+        if key[0].type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise CavpError("fmeasure thresholds would be built during hipGraph capture; run one eager call first")
+        host = torch.linspace(0, 1 - 1e-10, int(pr_num))
+        if pr_num > 1 and not bool((host[1:] >= host[:-1]).all()):
+            raise CavpError("fmeasure: threshold table is not ascending")
+        th = host.to(device)
+        _thresholds[key] = th
+    return th
+
+
+def fmeasure_from_hist(hist: torch.Tensor, beta2: float = 0.3):
+    """Eval_Fmeasure's arithmetic from the per-image histograms hist[N, 2, pr_num + 1] (cavp_fmeasure_hist), on hist's device.
+    Returns (prec [N, pr_num], recall [N, pr_num], score [pr_num]); frames whose gt is all zero are skipped as in the reference.
+    Suffix sums of the histogram are y_temp.sum() and tp of every threshold; the float32 steps are the reference's."""
+    h = hist.to(torch.int64)
+    suf = h.flip(-1).cumsum(-1).flip(-1)           # suf[..., b] = #pixels with bin >= b
+    n = h.shape[0]
+    tp = suf[:, 1, 1:].float()                     # (y_temp * y).sum() for threshold i: bin >= i + 1
+    prec = tp / (suf[:, 0, 1:].float() + 1e-20)
+    ysum = suf[:, 1, :1].float()
+    recall = tp / (ysum + 1e-20)
+    f_score = (1 + beta2) * prec * recall / (beta2 * prec + recall)
+    f_score = f_score.masked_fill(f_score != f_score, 0)
+    valid = ysum[:, 0] > 0
+    avg_f = torch.where(valid[0], f_score[0], 0.0)
+    for i in range(1, n):
+        avg_f = avg_f + torch.where(valid[i], f_score[i], 0.0)
+    img_num = valid.sum().float()
+    # `avg_f / img_num` with a Python int: torch multiplies a device tensor by the float32 reciprocal, a CPU tensor it divides
+    score = avg_f * (1.0 / img_num) if avg_f.is_cuda else avg_f / img_num
+    score = torch.where(img_num > 0, score, 0.0)
+    return prec, recall, score
+
+
+def fmeasure_curve(pred, gt, pr_num=255, channel=1, hist_out=None) -> torch.Tensor:
+    """Eval_Fmeasure's averaged score curve [pr_num] as a device tensor (no host sync).  pred: probabilities [N, H, W] with dense
+    H x W planes (the images may be strided, e.g. torch.softmax(logits, 1)[:, 1]), or logits [N, C, H, W] whose softmax channel `channel` is the probability (computed in the kernel).  gt: [N, H, W] float32 or
+    int64 binary mask.  hist_out: optional int32 [N, 2, pr_num + 1] buffer (cleared here) for graph capture."""
+    if pred.dim() not in (3, 4) or gt.dim() != 3 or gt.shape[0] != pred.shape[0] or tuple(gt.shape[1:]) != tuple(pred.shape[-2:]):
+        raise CavpError(f"Eval_Fmeasure: pred [N, H, W] (or logits [N, C, H, W]) and gt [N, H, W] required, got "
+                        f"{tuple(pred.shape)} / {tuple(gt.shape)}")
+    ops._need_gpu(pred, gt)
+    th = thresholds(pr_num, pred.device)
+    shape = (pred.shape[0], 2, int(pr_num) + 1)
+    hist = _zeros(shape, torch.int32, pred.device) if hist_out is None else _zero_(hist_out)
+    ops.fmeasure_hist(pred, gt, th, hist, channel)
+    return fmeasure_from_hist(hist)[2]
+
+
+def Eval_Fmeasure(pred, gt, measure_path="", pr_num=255, channel=1):
+    """Best F-measure (beta^2 = 0.3) over `pr_num` thresholds, averaged over the frames whose gt is not all zero, as a Python
+    float.  pred: probabilities [N, H, W] (dense H x W planes; a strided view such as torch.softmax(logits, 1)[:, 1] is read in
+    place) or logits [N, C, H, W] (softmax channel `channel` taken in the kernel); gt: binary mask [N, H, W].  measure_path is
+    accepted and unused."""
+    return fmeasure_curve(pred, gt, pr_num, channel).max().item()

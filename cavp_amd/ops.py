@@ -464,3 +464,87 @@ def conv_smallcin_kxk(x_nchw: torch.Tensor, w_oihw: torch.Tensor, bias, out: tor
                                                  C.c_void_p(_stream()))
     _lib.check(st, "cavp_conv_smallcin_kxk_nchw")
     return out
+
+
+# ---- validation metrics (cavp_amd/metrics.py) -----------------------------------------------------------------------
+_METRIC_CODE = {torch.float32: F32, torch.int64: _lib.I64}
+
+
+def _metric_code(t: torch.Tensor, what: str) -> int:
+    try:
+        return _METRIC_CODE[t.dtype]
+    except KeyError:
+        raise _lib.CavpError(f"{what}: dtype {t.dtype} unsupported (float32 or int64)") from None
+
+
+def seg_confusion(logits: torch.Tensor, labels: torch.Tensor, num_classes: int, ignore: int, M: torch.Tensor) -> torch.Tensor:
+    """M[(K+1) * K] (int64, read as u64 counts) += the confusion counts of argmax_c(logits) against labels (include/cavp_hip.h,
+    cavp_seg_confusion_nchw).  logits: dense f32 [N, C, H, W]; labels: dense [N, H, W], int64 or float32 holding integers
+    (masks); K = num_classes >= C."""
+    _need_gpu(logits, labels, M)
+    if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise _lib.CavpError(f"seg_confusion: dense float32 [N, C, H, W] logits required, got {logits.dtype} {tuple(logits.shape)}")
+    n, c, h, w = logits.shape
+    if tuple(labels.shape) != (n, h, w) or not labels.is_contiguous():
+        raise _lib.CavpError(f"seg_confusion: dense labels of shape {(n, h, w)} required, got {tuple(labels.shape)}")
+    k = int(num_classes)
+    if k < c:
+        raise _lib.CavpError(f"seg_confusion: num_classes {k} < logit channels {c}")
+    if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
+        raise _lib.CavpError("seg_confusion: M must be a dense int64 tensor of (K+1)*K counts")
+    st = _lib.load().cavp_seg_confusion_nchw(_ptr(logits), _ptr(labels), _metric_code(labels, "seg_confusion"), n, c, h * w, k,
+                                             int(ignore), _ptr(M), C.c_void_p(_stream()))
+    _lib.check(st, f"cavp_seg_confusion_nchw N{n} C{c} HW{h * w} K{k}")
+    return M
+
+
+def mask_iou_stats(pred: torch.Tensor, target: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[N, 4] (int64) += per image (sum p*t, sum max(p, t), sum (1-t)(1-p), sum t); pred / target dense [N, H, W] of int64 or
+    float32 (float values must be integers: masks)."""
+    _need_gpu(pred, target, out)
+    if pred.dim() != 3 or pred.shape != target.shape:
+        raise _lib.CavpError(f"mask_iou_stats: pred and target must be [N, H, W] of one shape, got {tuple(pred.shape)} / {tuple(target.shape)}")
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise _lib.CavpError("mask_iou_stats: dense tensors required")
+    n, h, w = pred.shape
+    if out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != 4 * n:
+        raise _lib.CavpError("mask_iou_stats: out must be a dense int64 [N, 4] tensor")
+    st = _lib.load().cavp_mask_iou_stats(_ptr(pred), _metric_code(pred, "mask_iou_stats"), _ptr(target),
+                                         _metric_code(target, "mask_iou_stats"), n, h * w, _ptr(out), C.c_void_p(_stream()))
+    _lib.check(st, "cavp_mask_iou_stats")
+    return out
+
+
+def fmeasure_hist(src: torch.Tensor, gt: torch.Tensor, thresholds: torch.Tensor, hist: torch.Tensor, channel: int = 1) -> torch.Tensor:
+    """hist[N, 2, pr_num + 1] (int32, read as u32 counts) += per image the histogram of bin(p) = #{i : thresholds[i] <= p} over all
+    pixels ([n, 0]) and over gt != 0 ([n, 1]).  src: a probability map f32 [N, H, W] whose H x W planes are dense (the images may
+    be strided, as in torch.softmax(logits, 1)[:, 1]), or dense f32 logits [N, C, H, W] whose softmax channel `channel` is p;
+    gt: dense [N, H, W] float32 or int64; thresholds: ascending f32 [pr_num]."""
+    _need_gpu(src, gt, thresholds, hist)
+    if src.dtype != torch.float32 or src.dim() not in (3, 4):
+        raise _lib.CavpError(f"fmeasure_hist: float32 [N, H, W] probabilities or [N, C, H, W] logits required, got {tuple(src.shape)}")
+    n, h, w = (src.shape[0], src.shape[-2], src.shape[-1])
+    c = src.shape[1] if src.dim() == 4 else 0
+    if c:
+        if not src.is_contiguous():
+            raise _lib.CavpError("fmeasure_hist: dense [N, C, H, W] logits required")
+        ld = c * h * w
+    else:
+        if (w > 1 and src.stride(2) != 1) or (h > 1 and src.stride(1) != w):
+            raise _lib.CavpError(f"fmeasure_hist: the H x W planes of the probability map must be dense, got stride {src.stride()}")
+        ld = src.stride(0) if n > 1 else h * w
+        if ld < h * w:
+            raise _lib.CavpError(f"fmeasure_hist: overlapping probability planes (stride {src.stride()})")
+    if c == 1 or (c and not 0 <= channel < c):
+        raise _lib.CavpError(f"fmeasure_hist: logits need C >= 2 and 0 <= channel < C (C={c}, channel={channel})")
+    if tuple(gt.shape) != (n, h, w) or not gt.is_contiguous():
+        raise _lib.CavpError(f"fmeasure_hist: dense gt of shape {(n, h, w)} required, got {tuple(gt.shape)}")
+    pr = thresholds.numel()
+    if thresholds.dtype != torch.float32 or not thresholds.is_contiguous() or pr < 1:
+        raise _lib.CavpError("fmeasure_hist: dense float32 thresholds required")
+    if hist.dtype != torch.int32 or not hist.is_contiguous() or hist.numel() != n * 2 * (pr + 1):
+        raise _lib.CavpError("fmeasure_hist: hist must be a dense int32 [N, 2, pr_num + 1] tensor")
+    st = _lib.load().cavp_fmeasure_hist(_ptr(src), ld, _ptr(gt), _metric_code(gt, "fmeasure_hist"), _ptr(thresholds), n, c,
+                                        int(channel), h * w, pr, _ptr(hist), C.c_void_p(_stream()))
+    _lib.check(st, "cavp_fmeasure_hist")
+    return hist

@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-#define CAVP_ABI_VERSION 12
+#define CAVP_ABI_VERSION 13
 
-typedef enum { CAVP_F32 = 0, CAVP_BF16 = 1 } cavp_dtype_t;
+typedef enum { CAVP_F32 = 0, CAVP_BF16 = 1, CAVP_I64 = 2 /* ABI 13: metrics inputs only */ } cavp_dtype_t;
 typedef enum { CAVP_ACT_NONE = 0, CAVP_ACT_RELU = 1, CAVP_ACT_LEAKY = 2, CAVP_ACT_GELU = 3 } cavp_act_t;
 typedef enum {
   CAVP_OK = 0,
@@ -526,6 +526,30 @@ int cavp_space_to_depth(int32_t dtype, const void* src, void* dst, int32_t B, in
  * gradient sample_scale[b] * g.  per_sample = elements per batch item. */
 int cavp_row_scale_add(int32_t dtype, const void* x, const void* branch, const float* sample_scale, void* out, int32_t B,
                        int64_t per_sample, void* stream);
+
+/* ---- validation metrics (ABI 13; utils/eval_utils.py MIoU / ForegroundDetect, utils/avsbench_utils.py mask_iou / Eval_Fmeasure) ----
+ * Integer counts only, accumulated with integer atomics: results are independent of arrival order.  The float finalisation stays
+ * on the host side (cavp_amd/metrics.py), in the reference's expressions.  None of these clears its output (cavp_zero_bytes). */
+#define CAVP_METRICS_MAX_CLASSES 4096
+#define CAVP_FMEASURE_MAX_THRESHOLDS 4096
+/* M[row][p] += 1 ((K+1) x K, u64) for every pixel of f32 NCHW logits [N][C][HW] (dense; any 4-byte aligned base) with label
+ * t = labels[n][hw] (dense [N][HW]; label_dtype CAVP_I64, or CAVP_F32 holding integers - a non-finite one is not counted) where
+ * t >= 0 and t != ignore: p = argmax_c (first maximal index, a NaN counts as the maximum, as torch.max), row = t < K ? t : K.
+ * MIoU's inter / union / correct / labeled and ForegroundDetect's confusion matrix (M[:K]) follow exactly.  K >= C.  16-byte
+ * loads when HW % 4 == 0 and both bases are 16-byte aligned. */
+int cavp_seg_confusion_nchw(const float* logits, const void* labels, int32_t label_dtype, int32_t N, int32_t C, int64_t HW,
+                            int32_t K, int64_t ignore, uint64_t* M, void* stream);
+/* out[n][0..3] += (sum p*t, sum max(p, t), sum (1-t)*(1-p), sum t) over the HW pixels of image n; pred / target dense [N][HW] of
+ * CAVP_I64 or CAVP_F32 (f32 values must be integers, i.e. masks: they are converted to int64 per pixel). */
+int cavp_mask_iou_stats(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t N, int64_t HW,
+                        int64_t* out, void* stream);
+/* hist[n][0][b] / hist[n][1][b] += pixels of image n with bin b = #{i < pr_num : thresholds[i] <= p}, over all pixels / over
+ * gt != 0 (gt dense [N][HW], CAVP_F32 or CAVP_I64); thresholds ascending.  C == 0: src is a probability map whose image n is the
+ * dense plane src + n * src_image_stride (>= HW; e.g. torch.softmax(logits, 1)[:, 1], stride C * HW); C >= 2: src is f32 logits,
+ * image n = src + n * src_image_stride (>= C * HW) as [C][HW], and p = softmax over C, channel `channel`.
+ * hist: u32 [N][2][pr_num + 1]. */
+int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, const void* gt, int32_t gt_dtype, const float* thresholds, int32_t N, int32_t C,
+                       int32_t channel, int64_t HW, int32_t pr_num, uint32_t* hist, void* stream);
 
 #ifdef __cplusplus
 }
