@@ -46,14 +46,15 @@ def _s():
 
 def conv2d_dgrad(dy: torch.Tensor, w_t: torch.Tensor, dx: torch.Tensor, *, kh: int, kw: int, stride: int, pad: int,
                  dil: int, residual: Optional[torch.Tensor] = None, scale=None, shift=None, act: int = 0,
-                 mul: Optional[torch.Tensor] = None, bnb: Optional[dict] = None):
+                 mul: Optional[torch.Tensor] = None, bnb: Optional[dict] = None, tile: int = 0):
     """Data gradient of a forward conv (kh x kw, stride, pad, dil): dx = conv_transpose(dy, w) [* mul] (+ residual).
     mul (dx's shape): element-wise multiplier applied in the epilogue - the gelu' tensor of a fused fc1 + GELU forward.
     dy: [N,Ho,Wo,Cout_f] view, w_t: cavp_pack_weight_dgrad weights [Cin_f][kh][kw][Cout_f], dx: [N,H,W,Cin_f] view.
     bnb (dx is the gradient of a BatchNorm + activation output): dict(z, out | None, scale, shift, mean, rstd, act) - the launch
     stores dx * act'(.) and writes the BatchNorm-backward partial sums per pixel tile (cavp_conv2d_nhwc_bnbwd).  Returns
     (partials f32 [tiles][C][2], tiles) then - or, with bnb["sums"] (pre-zeroed f32 [2][C]: the tiles add into it with atomics),
-    (sums, 0) - or None when this launch cannot carry them (dx is then the plain gradient)."""
+    (sums, 0) - or None when this launch cannot carry them (dx is then the plain gradient).
+    tile: igemm tile id as in ops.conv2d (0 = the planner's choice; a forced tile is for tests and sweeps)."""
     _need_gpu(dy, w_t, dx, residual)
     lib = _lib.load()
     n, ho, wo, cof, ldx = _nhwc(dy)
@@ -74,7 +75,7 @@ def conv2d_dgrad(dy: torch.Tensor, w_t: torch.Tensor, dx: torch.Tensor, *, kh: i
         if (mn, mh, mw, mc) != (n, h, w, cif) or mul.dtype != dy.dtype:
             raise _lib.CavpError("conv2d_dgrad: mul must match dx")
     d = ConvDesc(dtype=dtype_code(dy.dtype), N=n, H=ho, W=wo, Cin=cof, ldx=ldx, Cout=cif, ldy=ldy, KH=kh, KW=kw,
-                 stride=1, pad=padt, dil=dil, ldr=ldr, act=act, splitk=0, tile=0, up=stride, Ho=h, Wo=w, stride_w=0,
+                 stride=1, pad=padt, dil=dil, ldr=ldr, act=act, splitk=0, tile=tile, up=stride, Ho=h, Wo=w, stride_w=0,
                  aux_mode=2 if mul is not None else 0, ld_aux=ld_aux)
     if stride == 1:
         eh, ew = ho + 2 * padt - dil * (kh - 1), wo + 2 * padt - dil * (kw - 1)

@@ -33,7 +33,7 @@ def _run(case, **kw):
     xv, _ = _to_nhwc_dev(x, BF)
     wp = ops.pack_weight(wt.to(DEV), BF)
     ref = F.conv2d(_q(x, BF), _q(wt, BF), None, s, p, d)
-    out = torch.empty((n, ref.shape[2], ref.shape[3], cout), dtype=BF, device=DEV)
+    out = torch.full((n, ref.shape[2], ref.shape[3], cout), float("nan"), dtype=BF, device=DEV)
     ops.conv2d(xv, wp, out, kh=k, kw=k, stride=s, pad=p, dil=d, **kw)
     return out, ref, (xv, wp)
 
@@ -53,10 +53,10 @@ def test_big_tile_is_race_free(case):
     out0, ref, (xv, wp) = _run(case, tile=BIG)
     first = out0.clone()
     for _ in range(5):
-        out = torch.empty_like(first)
+        out = torch.full_like(first, float("nan"))
         ops.conv2d(xv, wp, out, kh=k, kw=k, stride=s, pad=p, dil=d, tile=BIG)
         assert torch.equal(out, first), name + ": repeats differ"
-    small = torch.empty_like(first)
+    small = torch.full_like(first, float("nan"))
     ops.conv2d(xv, wp, small, kh=k, kw=k, stride=s, pad=p, dil=d, tile=1)
     err = float((small.float() - first.float()).abs().max())
     assert err <= 2e-2 * max(1.0, float(ref.abs().max())), (name, err)

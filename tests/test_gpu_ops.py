@@ -83,7 +83,7 @@ def test_conv_igemm_tiles(case, tile, dtype):
     xv, _ = _to_nhwc_dev(x, dtype)
     wp = ops.pack_weight(wt.to(DEV), dtype)
     ref = F.conv2d(_q(x, dtype), _q(wt, dtype), None, s, p, d)
-    out = torch.empty((n, ref.shape[2], ref.shape[3], cout), dtype=dtype, device=DEV)
+    out = torch.full((n, ref.shape[2], ref.shape[3], cout), float("nan"), dtype=dtype, device=DEV)
     ops.conv2d(xv, wp, out, kh=k, kw=k, stride=s, pad=p, dil=d, tile=tile)
     _check(out.permute(0, 3, 1, 2), ref, dtype, f"{name}/tile{tile}")
 
@@ -97,7 +97,7 @@ def test_conv_splitk(splitk, dtype):
     bias = _rand(cout, seed=5)
     xv, _ = _to_nhwc_dev(x, dtype)
     ref = F.relu(F.conv2d(_q(x, dtype), _q(wt, dtype), bias, 1, 1, 1))
-    out = torch.empty((n, h, w, cout), dtype=dtype, device=DEV)
+    out = torch.full((n, h, w, cout), float("nan"), dtype=dtype, device=DEV)
     ops.conv2d(xv, ops.pack_weight(wt.to(DEV), dtype), out, kh=3, kw=3, pad=1, shift=bias.to(DEV), act=ops.ACT_RELU,
                splitk=splitk)
     _check(out.permute(0, 3, 1, 2), ref, dtype, f"splitk{splitk}")
@@ -111,7 +111,7 @@ def test_conv_classifier_small_cout(cout, dtype):
     x, wt, b = _rand(2, 256, 12, 10, seed=6), _rand(cout, 256, 1, 1, seed=7, scale=0.06), _rand(cout, seed=8)
     xv, _ = _to_nhwc_dev(x, dtype)
     ref = F.conv2d(_q(x, dtype), _q(wt, dtype), b)
-    out = torch.empty((2, 12, 10, cout), dtype=dtype, device=DEV)
+    out = torch.full((2, 12, 10, cout), float("nan"), dtype=dtype, device=DEV)
     ops.conv2d(xv, ops.pack_weight(wt.to(DEV), dtype), out, shift=b.to(DEV))
     _check(out.permute(0, 3, 1, 2), ref, dtype, f"cls{cout}")
 

@@ -69,7 +69,7 @@ def test_conv_dgrad_wgrad(case, dt):
     dyv = _nhwc(dy, dt)
     # dgrad (+ accumulate into an existing gradient through the residual input)
     prev = _q(_rand(n, cin, h, w, seed=4), dt)
-    dx = torch.empty((n, h, w, cin), dtype=dt, device=DEV)
+    dx = torch.full((n, h, w, cin), float("nan"), dtype=dt, device=DEV)
     wT = T.pack_weight_dgrad(wt.detach().to(DEV), dt)
     T.conv2d_dgrad(dyv, wT, dx, kh=k, kw=k, stride=s, pad=p, dil=d, residual=_nhwc(prev, dt))
     _check(dx.permute(0, 3, 1, 2), x.grad + prev, dt, name + ".dgrad")
@@ -615,12 +615,12 @@ def test_conv_dgrad_fused_bn_backward_stats(case, dt):
     # plain launch: gradient of a (+ what the skip path already put there)
     dyv = _nhwc(dy, dt)
     wT = T.pack_weight_dgrad(wt.to(DEV), dt)
-    plain = torch.empty((n, h, w, cin), dtype=dt, device=DEV)
+    plain = torch.full((n, h, w, cin), float("nan"), dtype=dt, device=DEV)
     T.conv2d_dgrad(dyv, wT, plain, kh=k, kw=k, stride=s, pad=p, dil=d, residual=_nhwc(prev, dt) if prev is not None else None)
     # fused launch
     zv = _nhwc(z, dt)
     outv = _nhwc(a_q, dt) if with_out else None
-    g = torch.empty((n, h, w, cin), dtype=dt, device=DEV)
+    g = torch.full((n, h, w, cin), float("nan"), dtype=dt, device=DEV)
     mean_d, rstd_d, sc_d, sh_d = (t.float().to(DEV) for t in (mean, rstd, scale, shift))
     r = T.conv2d_dgrad(dyv, wT, g, kh=k, kw=k, stride=s, pad=p, dil=d, residual=_nhwc(prev, dt) if prev is not None else None,
                        bnb=dict(z=zv, out=outv, scale=sc_d, shift=sh_d, mean=mean_d, rstd=rstd_d, act=ops.ACT_RELU))

@@ -58,7 +58,7 @@ def main():
         ref = {ops.ACT_NONE: ref, ops.ACT_RELU: ref.relu(), ops.ACT_LEAKY: F.leaky_relu(ref, 0.01)}[act].float()
         xd = x.permute(0, 2, 3, 1).contiguous().to(dt).to(DEV)
         wp = ops.pack_weight(wt.to(DEV), dt)
-        out = torch.empty((n, ho, wo, cout), dtype=dt, device=DEV)
+        out = torch.full((n, ho, wo, cout), float("nan"), dtype=dt, device=DEV)
         desc = f"case {case}: {str(dt)[6:]} N{n} {h}x{w} {cin}->{cout} k{k} s{stride} p{pad} d{dil} act{act} res{int(use_res)}"
         try:
             ops.conv2d(xd, wp, out, kh=k, kw=k, stride=stride, pad=pad, dil=dil, scale=sc.to(DEV), shift=sh.to(DEV),
@@ -74,7 +74,7 @@ def main():
             ok_d = ok_w = True
             e_d = e_w = 0.0
             if pad <= dil * (k - 1):
-                dx = torch.empty((n, h, w, cin), dtype=dt, device=DEV)
+                dx = torch.full((n, h, w, cin), float("nan"), dtype=dt, device=DEV)
                 T.conv2d_dgrad(gyd, T.pack_weight_dgrad(wt.to(DEV), dt), dx, kh=k, kw=k, stride=stride, pad=pad, dil=dil)
                 e_d = float((dx.float().cpu().permute(0, 3, 1, 2) - xr.grad.float()).abs().max())
                 ok_d = e_d <= (3e-2 if dt == torch.bfloat16 else 3e-4) * max(1.0, float(xr.grad.abs().max()))
