@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(HERE, "libcavp_hip.so")
 
 F32, BF16, I64 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_GELU = 0, 1, 2, 3
-ABI_VERSION = 13
+ABI_VERSION = 14
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH = -1, -2, -3, -4, -5   # cavp_status_t
 WGRAD_GROUP_MAX = 16   # CAVP_WGRAD_GROUP_MAX
 
@@ -130,6 +130,14 @@ PROTOTYPES = {
     "cavp_symm_add": (_i32, [_vp, _vp, _i32, _f32, _vp]),
     "cavp_symm_add_scaled": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
     "cavp_l2norm_bwd_scatter": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _vp]),
+    # ---- contrastive loss, device-side sampling (ABI 14) ----
+    "cavp_contrast_sample_work_bytes": (_sz, [_i32]),
+    "cavp_contrast_sample": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_gather_l2norm_dev": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp,
+                                      _vp]),
+    "cavp_infonce_rows_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _f32, _vp]),
+    "cavp_l2norm_bwd_scatter_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64,
+                                           _vp]),
     # ---- PVTv2 ----
     "cavp_sra_attention": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "cavp_dwconv3x3_nhwc": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

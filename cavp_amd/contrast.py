@@ -9,6 +9,10 @@ Split of work:
   device - L2-normalise + gather of the N anchors, S = A A^T / T on the f32 MFMA igemm, the row-wise InfoNCE, and the
            whole backward (dS, (dS + dS^T) A via the wgrad GEMM, normalisation backward, scatter into the feature
            gradient) - libcavp_hip.so only, no torch arithmetic.
+
+Opt-in: `ContrastLoss.use_device_sampler(max_classes)` moves the sampling onto the device as well (same selection rule,
+Philox4x32-10 keys instead of torch.randperm; include/cavp_hip.h ABI 14).  That path never touches the host between its
+launches, so `loss = crit(...); loss.backward()` can be captured in a hipGraph.
 """
 from __future__ import annotations
 
@@ -79,15 +83,20 @@ def downsample_labels(gt: torch.Tensor, size: Tuple[int, int]) -> np.ndarray:
     return g[:, hi][:, :, wi].reshape(g.shape[0], -1)
 
 
+def _label_nearest_device(gt: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """[B, H, W] device labels -> int32 [B, h, w] on the device (cavp_label_nearest); no host involvement."""
+    g = gt.detach()
+    if g.dtype != torch.int64 or not g.is_contiguous():
+        g = g.to(torch.int64).contiguous()
+    out = torch.empty((g.shape[0], size[0], size[1]), dtype=torch.int32, device=g.device)
+    _lib.check(_lib.load().cavp_label_nearest(_ptr(g), _ptr(out), g.shape[0], g.shape[1], g.shape[2], size[0], size[1],
+                                              C.c_void_p(_stream())), "cavp_label_nearest")
+    return out
+
+
 def _downsample_labels_device(gt: torch.Tensor, size: Tuple[int, int]) -> np.ndarray:
-    if True:
-        g = gt.detach()
-        if g.dtype != torch.int64 or not g.is_contiguous():
-            g = g.to(torch.int64).contiguous()
-        out = torch.empty((g.shape[0], size[0], size[1]), dtype=torch.int32, device=g.device)
-        _lib.check(_lib.load().cavp_label_nearest(_ptr(g), _ptr(out), g.shape[0], g.shape[1], g.shape[2], size[0], size[1],
-                                                  C.c_void_p(_stream())), "cavp_label_nearest")
-        return out.cpu().numpy().astype(np.int64).reshape(g.shape[0], -1)
+    out = _label_nearest_device(gt, size)
+    return out.cpu().numpy().astype(np.int64).reshape(out.shape[0], -1)
 
 
 _PINNED: dict = {}
@@ -224,6 +233,84 @@ class _InfoNCEFn(torch.autograd.Function):
         return grads[0], grads[1], None, None, None
 
 
+class DevicePlan:
+    """What the device sampler chose in one call; every field is a device tensor.  header: int32[8] = {n, n_match, k_kept,
+    sample_num, offset_lo, offset_hi, seed_lo, seed_hi}; idx_b / idx_p / labels: int32[cap] (rows >= n hold -1)."""
+    __slots__ = ("header", "idx_b", "idx_p", "labels", "cap", "work", "gm", "gs")
+
+    def __init__(self, header, idx_b, idx_p, labels, cap, work, gm, gs):
+        self.header, self.idx_b, self.idx_p, self.labels, self.cap, self.work, self.gm, self.gs = \
+            header, idx_b, idx_p, labels, cap, work, gm, gs
+
+
+def sample_anchors_device(gm: torch.Tensor, gs: torch.Tensor, ignore_idx: int, max_views: int, max_classes: int,
+                          state: torch.Tensor) -> DevicePlan:
+    """cavp_contrast_sample on the reduced int32 label maps [B, h, w]: three launches, nothing read by the host.  `state` is the
+    sampler's persistent int64[4] = {seed, offset, dropped_classes, bad_labels}."""
+    lib = _lib.load()
+    dev = gm.device
+    total, hw = gm.numel(), gm.shape[1] * gm.shape[2]
+    cap = (max_classes + 2) * max_views
+    # one allocation: header | idx_b | idx_p | labels; the kernels' scratch in a second one
+    buf = torch.empty(8 + 3 * cap, dtype=torch.int32, device=dev)
+    header, ib, ip, lab = buf[:8], buf[8:8 + cap], buf[8 + cap:8 + 2 * cap], buf[8 + 2 * cap:]
+    work = torch.empty(lib.cavp_contrast_sample_work_bytes(max_classes) // 4, dtype=torch.int32, device=dev)
+    _lib.check(lib.cavp_contrast_sample(_ptr(gm), _ptr(gs), total, hw, int(ignore_idx), max_views, max_classes, _ptr(state),
+                                        _ptr(header), _ptr(work), _ptr(ib), _ptr(ip), _ptr(lab), C.c_void_p(_stream())),
+               "cavp_contrast_sample")
+    return DevicePlan(header, ib, ip, lab, cap, work, gm, gs)
+
+
+class _InfoNCEDeviceFn(torch.autograd.Function):
+    """_InfoNCEFn with the anchor count on the device: every buffer has the static capacity of the plan, the kernels read n and
+    n_match from the plan header.  No host decision depends on a device value, in either direction."""
+
+    @staticmethod
+    def forward(ctx, em, es, plan: DevicePlan, temperature: float, eps: float):
+        lib = _lib.load()
+        dev = em.device
+        st = C.c_void_p(_stream())
+        Cc = em.shape[1]
+        cap, npad = plan.cap, (plan.cap + 3) // 4 * 4
+        A = torch.empty((npad, Cc), dtype=torch.float32, device=dev)
+        norms = torch.empty(npad, dtype=torch.float32, device=dev)
+        _lib.check(lib.cavp_gather_l2norm_dev(_ptr(em), *_strides_bcp(em), _ptr(es), *_strides_bcp(es), _ptr(plan.header),
+                                              _ptr(plan.idx_b), _ptr(plan.idx_p), cap, npad, Cc, C.c_float(1e-12), _ptr(A),
+                                              _ptr(norms), st), "cavp_gather_l2norm_dev")
+        S = torch.empty((npad, npad), dtype=torch.float32, device=dev)
+        inv_t = torch.full((npad,), 1.0 / temperature, dtype=torch.float32, device=dev)
+        ops.linear(A, A.view(npad, 1, 1, Cc), S, scale=inv_t)          # S = A A^T / T at the static capacity
+        rows = torch.empty(npad, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        need_grad = em.requires_grad or es.requires_grad
+        dS = torch.empty_like(S) if need_grad else None
+        _lib.check(lib.cavp_infonce_rows_dev(_ptr(S), _ptr(plan.labels), _ptr(plan.header), cap, npad, C.c_float(eps), _ptr(rows),
+                                             _ptr(loss), _ptr(dS), C.c_float(1.0), st), "cavp_infonce_rows_dev")
+        ctx.saved = (A, norms, dS, plan, em, es, temperature)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        A, norms, dS, plan, em, es, temperature = ctx.saved
+        st = C.c_void_p(_stream())
+        npad, Cc = A.shape
+        G = torch.empty_like(dS)
+        gs = gout.detach().reshape(1).to(torch.float32)
+        _lib.check(lib.cavp_symm_add_scaled(_ptr(dS), _ptr(G), npad, C.c_float(1.0 / temperature), _ptr(gs), st), "cavp_symm_add_scaled")
+        dA = T.zeros((npad, Cc), torch.float32, A.device)
+        T.linear_wgrad(A, G, dA)
+        grads = []
+        for x in (em, es):
+            b, c, h, w = x.shape
+            grads.append(T.zeros((b, h, w, c), torch.float32, x.device))   # NHWC memory, cleared by a launch; NCHW views returned
+        (_, _, h, w), c = em.shape, Cc
+        _lib.check(lib.cavp_l2norm_bwd_scatter_dev(_ptr(dA), _ptr(A), _ptr(norms), _ptr(plan.header), _ptr(plan.idx_b),
+                                                   _ptr(plan.idx_p), plan.cap, Cc, _ptr(grads[0]), h * w * c, 1, c, _ptr(grads[1]),
+                                                   h * w * c, 1, c, st), "cavp_l2norm_bwd_scatter_dev")
+        return grads[0].permute(0, 3, 1, 2), grads[1].permute(0, 3, 1, 2), None, None, None
+
+
 class ContrastLoss(nn.Module):
     def __init__(self, temperature, ignore_idx, max_views):
         super().__init__()
@@ -232,6 +319,81 @@ class ContrastLoss(nn.Module):
         self.eps = 1e-12
         self.temperature = temperature
         self.max_views = max_views
+        self._dev = None           # device sampler: (max_classes, state int64[4]) once use_device_sampler() was called
+        self._last_plan = None
+
+    # ---- opt-in device-side sampling -------------------------------------------------------------------------------------
+    def use_device_sampler(self, max_classes: int, seed: int = 0, *, device=None) -> "ContrastLoss":
+        """Switch this instance to the device sampler: the class-balanced selection of contrastive_aud.py:76-141 with
+        Philox4x32-10 keys in place of torch.randperm (same distribution, another stream: the anchors differ from the host
+        sampler's and from the reference's for any seed).  After this call forward() and backward() make no device-to-host copy,
+        no host-to-device copy and no stream synchronisation and allocate through torch's caching allocator only, so
+        `with torch.cuda.graph(g): loss = crit(em, gt, es, gs); loss.backward()` works (after one eager warm-up call, which sizes
+        the GEMM workspace).  Every replay draws fresh anchors: the call counter lives on the device.
+
+        max_classes: the largest number of foreground classes that may qualify (>= max_views pixels) in one batch.  It fixes the
+        static anchor capacity Ncap = (max_classes + 2) * max_views at which the GEMMs run.  If more classes qualify, the
+        lowest-numbered max_classes are kept and the device counter `dropped_classes` grows by the surplus (last_plan()).
+
+        Differences from the default path: the loss is always 0-dim; when no class qualifies its value is 0 and both feature
+        gradients are zero (the reference returns a constant of shape [1] there - a shape cannot follow a device value without
+        a synchronisation).  Labels must lie in [0, 255]: the host cannot look at them without a copy, so the count kernel
+        counts the ones outside (they belong to no group) and last_plan() raises CavpError when there were any."""
+        if not isinstance(max_classes, int) or not 1 <= max_classes <= 254:
+            raise _lib.CavpError("use_device_sampler: 1 <= max_classes <= 254")
+        if not isinstance(self.max_views, int) or not 1 <= self.max_views <= 1024:
+            raise _lib.CavpError("the device sampler needs 1 <= max_views <= 1024")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._dev = (max_classes, torch.zeros(4, dtype=torch.int64, device=dev))
+        self._last_plan = None
+        self.manual_seed(seed)
+        return self
+
+    def manual_seed(self, seed: int) -> None:
+        """Reset the device sampler's seed and its call counter (offset 0).  A host-to-device write: not legal while a hipGraph
+        is being captured; graphs captured earlier see the new values on their next replay."""
+        if self._dev is None:
+            raise _lib.CavpError("manual_seed: call use_device_sampler() first (the host sampler follows torch.manual_seed)")
+        s = int(seed) & 0xFFFFFFFFFFFFFFFF
+        s = s - (1 << 64) if s >= (1 << 63) else s
+        self._dev[1][:2].copy_(torch.tensor([s, 0], dtype=torch.int64))
+
+    def last_plan(self) -> dict:
+        """The device tensors of the most recent device-sampler call (of the captured call, after a graph replay): `header`
+        int32[4] = {n, n_match, k_eligible (classes kept), sample_num}, `idx_b`, `idx_p`, `labels` (int32[Ncap], rows >= n hold
+        -1), `dropped_classes` (int64[1], cumulative), `seed_offset` (int32[4]: the offset and seed this call drew with, low /
+        high words).  For tests and debugging: it reads the bad-label counter, which synchronises - never call it in a capture.
+        Raises CavpError if a label outside [0, 255] was seen since the last check."""
+        if self._dev is None or self._last_plan is None:
+            raise _lib.CavpError("last_plan: no device-sampler call yet")
+        state, p = self._dev[1], self._last_plan
+        bad = int(state[3].item())
+        if bad:
+            state[3:4].zero_()
+            raise _lib.CavpError(f"ContrastLoss device sampler: {bad} label(s) outside [0, 255]")
+        return {"header": p.header[:4], "idx_b": p.idx_b, "idx_p": p.idx_p, "labels": p.labels,
+                "dropped_classes": state[2:3], "seed_offset": p.header[4:8]}
+
+    def _forward_device(self, embeds_match, gt_match, embeds_shuffle, gt_shuffle):
+        max_classes, state = self._dev
+        em, es = embeds_match, embeds_shuffle
+        if em.device != state.device:
+            raise _lib.CavpError(f"device sampler lives on {state.device}, features on {em.device}")
+        if em.dim() != 4 or em.shape != es.shape:
+            raise _lib.CavpError("ContrastLoss: embeds_match and embeds_shuffle must be [B, C, h, w] of one shape")
+        B, _, h, w = em.shape
+        if B * h * w >= 2 ** 31:
+            raise _lib.CavpError("the device sampler needs B*h*w < 2**31")
+        if not isinstance(self.max_views, int) or not 1 <= self.max_views <= 1024:
+            raise _lib.CavpError("the device sampler needs 1 <= max_views <= 1024")
+        for g in (gt_match, gt_shuffle):
+            if not g.is_cuda or g.dim() != 3 or g.shape[0] != B or g.is_floating_point() or g.dtype == torch.bool:
+                raise _lib.CavpError("the device sampler needs integer [B, H, W] label maps on the device")
+        _strides_bcp(em), _strides_bcp(es)
+        plan = sample_anchors_device(_label_nearest_device(gt_match, (h, w)), _label_nearest_device(gt_shuffle, (h, w)),
+                                     self.ignore_idx, self.max_views, max_classes, state)
+        self._last_plan = plan
+        return _InfoNCEDeviceFn.apply(em, es, plan, float(self.temperature), float(self.eps))
 
     @staticmethod
     def prefetch_labels(gt_match, gt_shuffle, size) -> None:
@@ -246,6 +408,8 @@ class ContrastLoss(nn.Module):
             raise _lib.CavpError("ContrastLoss (MI355X path) needs HIP device tensors: there is no CPU fallback")
         if embeds_match.dtype != torch.float32 or embeds_shuffle.dtype != torch.float32:
             raise _lib.CavpError("ContrastLoss expects the f32 out_fusion features")
+        if self._dev is not None:
+            return self._forward_device(embeds_match, gt_match, embeds_shuffle, gt_shuffle)
         size = tuple(embeds_match.shape[2:])
         plan = sample_anchors(downsample_labels(gt_match, size), downsample_labels(gt_shuffle, size), self.ignore_idx,
                               self.max_views)

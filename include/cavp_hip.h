@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CAVP_ABI_VERSION 13
+#define CAVP_ABI_VERSION 14
 
 typedef enum { CAVP_F32 = 0, CAVP_BF16 = 1, CAVP_I64 = 2 /* ABI 13: metrics inputs only */ } cavp_dtype_t;
 typedef enum { CAVP_ACT_NONE = 0, CAVP_ACT_RELU = 1, CAVP_ACT_LEAKY = 2, CAVP_ACT_GELU = 3 } cavp_act_t;
@@ -468,6 +468,38 @@ int cavp_symm_add_scaled(const float* d, float* g, int32_t n, float scale, const
 int cavp_l2norm_bwd_scatter(const float* dA, const float* A, const float* norms, const int32_t* idx_b,
                             const int32_t* idx_p, int32_t N, int32_t C, float* dx, int64_t stride_b, int64_t stride_c,
                             int64_t stride_p, void* stream);
+
+/* ---- ABI 14: device-side anchor sampling (opt-in; contrastive_aud.py:76-141 with a counter-based generator) ----
+ * The selection rule of extraction_samples with Philox4x32-10 in place of torch.randperm, so that the whole loss step runs
+ * without the host and can be captured in a hipGraph.  Pixel i = b*HW + p of the reduced label map has the 64-bit keys
+ *   key(stream, i) = (r0 << 32) | r1,  r = Philox4x32-10(counter = (i, stream, offset_lo, offset_hi), key = (seed_lo, seed_hi)),
+ * stream 0 = per-class pick, 1 = background, 2 = shuffle candidates; "pick q of a group" = its q members with the smallest
+ * (key, i), in ascending (key, i).  Rows: every kept class ascending (max_views each, label c), sample_num background pixels
+ * (label 0), sample_num of all match-foreground pixels (label gs[i]); sample_num = min(max_views, n_fg, n_bg); n = 0 when no class
+ * has max_views pixels.  Of more than max_classes qualifying classes the lowest-numbered are kept.
+ *   state  int64[4] (device, persistent): {seed, offset, dropped_classes, bad_labels}; a call reads seed / offset, then
+ *          offset += 1, dropped_classes += surplus classes, bad_labels += labels outside [0, 255] (such a pixel is in no group).
+ *   header int32[8]: {n, n_match, k_kept, sample_num, offset_lo, offset_hi, seed_lo, seed_hi} of this call.
+ *   work   cavp_contrast_sample_work_bytes(max_classes) bytes of scratch; idx_b / idx_p / labels: int32[cap], cap =
+ *          (max_classes + 2) * max_views; rows >= n are filled with -1.
+ * 1 <= max_views <= 1024, 1 <= max_classes <= 254, total = B*HW < 2^31.  Deterministic for a given (seed, offset). */
+size_t cavp_contrast_sample_work_bytes(int32_t max_classes);
+int cavp_contrast_sample(const int32_t* gm, const int32_t* gs, int64_t total, int32_t HW, int32_t ignore_idx, int32_t max_views,
+                         int32_t max_classes, int64_t* state, int32_t* header, int32_t* work, int32_t* idx_b, int32_t* idx_p,
+                         int32_t* labels, void* stream);
+/* The chain above with the anchor count read from `header` on the device.  rows (>= cap, the leading dimension of A / S) is
+ * static: rows >= n of A are zero-filled (norms 1), columns / rows >= n of S are ignored and dS is zero outside [n][n], the loss
+ * is 0 when n == 0, and the scatter skips rows >= n.  Rows < n_match read / write the match tensor, the others the shuffle one. */
+int cavp_gather_l2norm_dev(const float* xm, int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, const float* xs,
+                           int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p, const int32_t* header,
+                           const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t rows, int32_t C, float eps, float* A,
+                           float* norms, void* stream);
+int cavp_infonce_rows_dev(const float* S, const int32_t* labels, const int32_t* header, int32_t cap, int32_t ld, float eps,
+                          float* row_mlpp, float* loss, float* dS, float grad_scale, void* stream);
+int cavp_l2norm_bwd_scatter_dev(const float* dA, const float* A, const float* norms, const int32_t* header, const int32_t* idx_b,
+                                const int32_t* idx_p, int32_t cap, int32_t C, float* dxm, int64_t m_stride_b, int64_t m_stride_c,
+                                int64_t m_stride_p, float* dxs, int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p,
+                                void* stream);
 
 /* ---- PVTv2-B5 visual backbone (models/visual/backbones/pvt/pvt.py, config #4 / SURVEY.md §8a row a12) ---- */
 /* Attention.forward (pvt.py:102-130): softmax(q k^T * scale) v per head with the spatially-reduced K/V (Nk <= 256,

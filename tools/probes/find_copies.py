@@ -1,5 +1,6 @@
 """Where do the device-to-device copies / fills of a training step come from?  (torch.profiler, eager step of bench.py's model)
-usage: python tools/probes/find_copies.py [c4|c1p] [batch]"""
+usage: python tools/probes/find_copies.py [c4|c1p] [batch]
+       python tools/probes/find_copies.py c5copies | c5copies-device"""
 import sys, os, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -10,9 +11,10 @@ cfgname = sys.argv[1] if len(sys.argv) > 1 else "c4"
 dev = torch.device("cuda:0")
 
 
-def c5_copies():
+def c5_copies(device_sampler=False):
     """config #5 step (model on the graphed autograd node + torch CE + ContrastLoss): device-to-host / host-to-device copies of one
-    steady-state step.   python tools/probes/find_copies.py c5copies"""
+    steady-state step.   python tools/probes/find_copies.py c5copies
+    c5copies-device: the same step with ContrastLoss.use_device_sampler(); expected 0 and 0."""
     import torch.nn.functional as F
     from cavp_amd.contrast import ContrastLoss
     B = 30
@@ -23,6 +25,8 @@ def c5_copies():
     image, audio, label = [t.to(dev) for t in synth_inputs(B, cfg["hw"], audio_batch=2 * B, num_classes=cfg["C"], seed=100)]
     label_shuf = synth_inputs(B, cfg["hw"], audio_batch=2 * B, num_classes=cfg["C"], seed=900)[2].to(dev)
     crit = ContrastLoss(temperature=0.1, ignore_idx=255, max_views=512)
+    if device_sampler:
+        crit.use_device_sampler(max(1, cfg["C"] - 1))
 
     def step():
         model.zero_grad(set_to_none=True)
@@ -42,10 +46,11 @@ def c5_copies():
             c[ev.name] += 1
     print("copies in one steady-state config-#5 step:", dict(c))
     print("device-to-host copies:", sum(v for k, v in c.items() if "DtoH" in k or "Device -> Host" in k))
+    print("host-to-device copies:", sum(v for k, v in c.items() if "HtoD" in k or "Host -> Device" in k))
 
 
-if cfgname == "c5copies":
-    c5_copies()
+if cfgname in ("c5copies", "c5copies-device"):
+    c5_copies(device_sampler=cfgname.endswith("-device"))
 else:
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     cfg = bench.model_cfg(cfgname)
