@@ -11,7 +11,8 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("args", [["--cases", "60", "--seed", "11"], ["--cases", "16", "--seed", "12", "--large"]], ids=["small", "large"])
+@pytest.mark.parametrize("args", [["--cases", "60", "--seed", "11"], ["--cases", "16", "--seed", "12", "--large"],
+                                  ["--cases", "60", "--seed", "13", "--exact"]], ids=["small", "large", "exact"])
 def test_fuzz_conv(args):
     r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "fuzz_conv.py")] + args, cwd=REPO, stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=900)

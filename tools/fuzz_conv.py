@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised shapes through cavp_conv2d_nhwc (auto tile choice), its data gradient and its weight gradient against PyTorch on the
-CPU (bf16-rounded operands, f32 / f64 accumulation).  GPU box only.  usage: python tools/fuzz_conv.py [--cases 120] [--seed 0]"""
+CPU (bf16-rounded operands, f32 / f64 accumulation).  GPU box only.  usage: python tools/fuzz_conv.py [--cases 120] [--seed 0]
+--exact: the same random shapes on integer-lattice inputs (tests/_lattice.py: activations in {-2..2}, weights +-1, power-of-two scales,
+integer shifts and residuals), where the float64 reference is THE answer: every output must match it bit for bit, no tolerance."""
 import argparse
 import os
 import random
@@ -13,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cavp_amd import ops, train_ops as T  # noqa: E402
 
 DEV = "cuda:0"
+L = None   # tests/_lattice.py, imported by --exact alone: the tolerance modes need nothing outside cavp_amd
 
 
 def main():
@@ -20,7 +23,11 @@ def main():
     ap.add_argument("--cases", type=int, default=120)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--large", action="store_true", help="shapes that reach the 256x256 tile / split-K / deep-ring plans")
+    ap.add_argument("--exact", action="store_true", help="integer-lattice inputs, bit-exact comparison instead of the tolerances")
     a = ap.parse_args()
+    if a.exact:
+        global L
+        from tests import _lattice as L
     rng = random.Random(a.seed)
     bad = 0
     for case in range(a.cases):
@@ -52,6 +59,11 @@ def main():
         wt = q(torch.randn((cout, cin, k, k), generator=g) * (cin * k * k) ** -0.5)
         sc, sh = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
         res = q(torch.randn((n, cout, ho, wo), generator=g)) if use_res else None
+        if a.exact:   # scales rounded to powers of two, shifts to integers; gain 4 keeps scale * sum inside the bf16 integer range
+            x = L.activations((n, cin, h, w), cin * k * k, 5000 + case, gain=4.0)
+            wt = L.weights((cout, cin, k, k), 6000 + case)
+            sc, sh = torch.pow(2.0, torch.log2(sc).round()), (sh * 4).round()
+            res = L.ints((n, cout, ho, wo), -4, 4, 7000 + case) if use_res else None
         ref = F.conv2d(x.double(), wt.double(), None, stride, pad, dil) * sc.double()[None, :, None, None] + sh.double()[None, :, None, None]
         if use_res:
             ref = ref + res.double()
@@ -63,6 +75,9 @@ def main():
         try:
             ops.conv2d(xd, wp, out, kh=k, kw=k, stride=stride, pad=pad, dil=dil, scale=sc.to(DEV), shift=sh.to(DEV),
                        residual=res.permute(0, 2, 3, 1).contiguous().to(dt).to(DEV) if use_res else None, act=act)
+            if a.exact:
+                bad += exact_case(a, case, desc, dt, x, wt, sc, sh, res, act, (k, stride, pad, dil), xd, wp, out)
+                continue
             tol = (2e-2 if dt == torch.bfloat16 else 2e-4) * max(1.0, float(ref.abs().max()))
             err = float((out.float().cpu().permute(0, 3, 1, 2) - ref).abs().max())
             ok_f = err <= tol
@@ -94,6 +109,36 @@ def main():
                 print("ERROR", desc, msg[:160], flush=True)
     print(f"fuzz: {a.cases} cases, {bad} bad")
     return 1 if bad else 0
+
+
+def exact_case(a, case, desc, dt, x, wt, sc, sh, res, act, conv, xd, wp, out):
+    """forward (already launched into `out`), data gradient and weight gradient of one lattice case; returns 1 when any of them differs
+    from float64 in a single element"""
+    k, stride, pad, dil = conv
+    n, cin, h, w = x.shape
+    cout = wt.shape[0]
+    try:
+        ref = L.ref64_conv(x, wt, stride, pad, dil, scale=sc, shift=sh, residual=res, act=act).permute(0, 2, 3, 1)
+        if dt == torch.bfloat16:
+            L.bf16_magnitude_ok(ref, desc)
+        L.assert_exact(out, ref, dt, desc + " fwd", "nhwc")
+        gy = L.out_grads((n, cout, out.shape[1], out.shape[2]), cout * k * k, 8000 + case)
+        gyd = gy.permute(0, 2, 3, 1).contiguous().to(dt).to(DEV)
+        if pad <= dil * (k - 1):
+            want = L.ref64_dgrad(gy, wt, x.shape, stride, pad, dil).permute(0, 2, 3, 1)
+            if dt == torch.bfloat16:
+                L.bf16_magnitude_ok(want, desc + " dgrad")
+            dx = torch.full((n, h, w, cin), float("nan"), dtype=dt, device=DEV)
+            T.conv2d_dgrad(gyd, T.pack_weight_dgrad(wt.to(DEV), dt), dx, kh=k, kw=k, stride=stride, pad=pad, dil=dil)
+            L.assert_exact(dx, want, dt, desc + " dgrad", "nhwc")
+        dw = torch.zeros((cout, k, k, cin), dtype=torch.float32, device=DEV)
+        T.conv2d_wgrad(xd, gyd, dw, kh=k, kw=k, stride=stride, pad=pad, dil=dil)
+        L.assert_exact(dw.permute(0, 3, 1, 2), L.ref64_wgrad(x, gy, wt.shape, stride, pad, dil)[0], torch.float32, desc + " wgrad",
+                       ("o", "i", "kh", "kw"))
+    except AssertionError as ex:
+        print("FAIL", str(ex)[:400], flush=True)
+        return 1
+    return 0
 
 
 if __name__ == "__main__":
