@@ -8,6 +8,7 @@
 // multiples of 4, not of 8) fall between lanes and every access is one wide load or store - the first version used
 // 2-byte accesses, 5 per operand per row.  The per-head dot products are masked wave reductions (<= 8 heads).
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -255,7 +256,6 @@ __global__ __launch_bounds__(256) void attn_gate4_bwd_kernel(const T* __restrict
   }
 }
 
-inline bool dt_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
 inline bool shape_ok(int dtype, int heads, int hd, const void* a, const void* b, const void* c, const void* d) {
   const uintptr_t al = dtype == CAVP_F32 ? 15 : 7;
   return heads <= kMaxHeads && (hd % 4) == 0 && heads * hd <= 512 &&
@@ -273,17 +273,13 @@ extern "C" int cavp_attn_gate(int32_t dtype, const void* q, const void* k, const
   if (nbl > 16384) nbl = 16384;
   hipStream_t s = (hipStream_t)stream;
   if (heads == 4 && hd <= 128) {   // one DPP row per head
-    if (dtype == CAVP_F32)
-      attn_gate4_kernel<float><<<(int)nbl, 256, 0, s>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, attn, B, T, hd, scale, q_rows);
-    else
-      attn_gate4_kernel<bf16_t><<<(int)nbl, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, attn, B, T, hd, scale, q_rows);
-    return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+    cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+      attn_gate4_kernel<E><<<(int)nbl, 256, 0, s>>>((const E*)q, (const E*)k, (const E*)v, (E*)o, attn, B, T, hd, scale, q_rows); });
+    CHECK_LAUNCH();
   }
-  if (dtype == CAVP_F32)
-    attn_gate_kernel<float><<<(int)nbl, 256, 0, s>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, attn, B, T, heads, hd, scale, q_rows);
-  else
-    attn_gate_kernel<bf16_t><<<(int)nbl, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, attn, B, T, heads, hd, scale, q_rows);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+    attn_gate_kernel<E><<<(int)nbl, 256, 0, s>>>((const E*)q, (const E*)k, (const E*)v, (E*)o, attn, B, T, heads, hd, scale, q_rows); });
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_attn_gate_bwd(int32_t dtype, const void* dout, const void* q, const void* k, const void* v,
@@ -305,15 +301,13 @@ extern "C" int cavp_attn_gate_bwd(int32_t dtype, const void* dout, const void* q
   float* det = cavp_det_scratch(gx, B * heads * hd, &det_err);
   if (det_err) return CAVP_ERR_WORKSPACE;
   if (heads == 4 && hd <= 128) {
-    if (dtype == CAVP_F32)
-      attn_gate4_bwd_kernel<float><<<dim3(gx, B), 256, 0, s>>>((const float*)dout, (const float*)q, (const float*)k, (const float*)v, attn, dattn, (float*)dq, dk, dv, T, hd, scale, tpb, q_batch, det);
-    else
-      attn_gate4_bwd_kernel<bf16_t><<<dim3(gx, B), 256, 0, s>>>((const bf16_t*)dout, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, attn, dattn, (bf16_t*)dq, dk, dv, T, hd, scale, tpb, q_batch, det);
-  } else if (dtype == CAVP_F32)
-    attn_gate_bwd_kernel<float><<<dim3(gx, B), 256, 0, s>>>((const float*)dout, (const float*)q, (const float*)k, (const float*)v, attn, dattn, (float*)dq, dk, dv, T, heads, hd, scale, tpb, q_batch, det);
-  else
-    attn_gate_bwd_kernel<bf16_t><<<dim3(gx, B), 256, 0, s>>>((const bf16_t*)dout, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, attn, dattn, (bf16_t*)dq, dk, dv, T, heads, hd, scale, tpb, q_batch, det);
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+      attn_gate4_bwd_kernel<E><<<dim3(gx, B), 256, 0, s>>>((const E*)dout, (const E*)q, (const E*)k, (const E*)v, attn, dattn, (E*)dq, dk, dv, T, hd, scale, tpb, q_batch, det); });
+  } else {
+    cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+      attn_gate_bwd_kernel<E><<<dim3(gx, B), 256, 0, s>>>((const E*)dout, (const E*)q, (const E*)k, (const E*)v, attn, dattn, (E*)dq, dk, dv, T, heads, hd, scale, tpb, q_batch, det); });
+  }
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   if (det && cavp_det_finish(det, gx, B * heads * hd, dk, dv, s) != hipSuccess) return CAVP_ERR_LAUNCH;
   return CAVP_OK;
 }

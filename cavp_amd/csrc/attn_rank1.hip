@@ -18,6 +18,7 @@
 // Layout: a token row is handled by one wave, lane i < C / 8 owns channels 8 i .. 8 i + 7 (C <= 512, C % 8 == 0); u and p
 // slices live in registers (2 x H x 8 floats per lane); dot products are reduced with DPP row sums + two butterfly steps.
 #include "igemm_params.h"   // row16_sum
+#include "host_util.h"
 
 namespace {
 
@@ -438,7 +439,6 @@ __global__ __launch_bounds__(256) void attn1_finish_kernel(const float* __restri
 }
 
 inline bool ok_shape(int C, int heads) { return C > 0 && C <= 512 && C % 8 == 0 && heads == 4 && C % heads == 0 && C / heads <= 128; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int token_groups(int Tn, int batches, int waves = 2048) {   // workgroups (4 token rows each per trip) per batch item
   int g = (waves / 4 + batches - 1) / batches;
   if (g < 1) g = 1;
@@ -453,27 +453,23 @@ extern "C" int cavp_attn1_supported(int32_t C, int32_t heads) { return ok_shape(
 extern "C" int cavp_attn1_prepare(int32_t dtype, const float* wq, const float* wp, const void* k, const void* v, float* U, float* P,
                                   int32_t B, int32_t C, int32_t heads, float scale, void* stream) {
   if (!wq || !wp || !k || !v || !U || !P || B <= 0) return CAVP_ERR_BAD_ARG;
-  if ((dtype != CAVP_F32 && dtype != CAVP_BF16) || !ok_shape(C, heads)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype) || !ok_shape(C, heads)) return CAVP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    attn1_prepare_kernel<float><<<B * heads, 256, 0, s>>>(wq, wp, (const float*)k, (const float*)v, U, P, C, heads, scale);
-  else
-    attn1_prepare_kernel<bf16_t><<<B * heads, 256, 0, s>>>(wq, wp, (const bf16_t*)k, (const bf16_t*)v, U, P, C, heads, scale);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+    attn1_prepare_kernel<E><<<B * heads, 256, 0, s>>>(wq, wp, (const E*)k, (const E*)v, U, P, C, heads, scale); });
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_attn1_fwd(int32_t dtype, const void* x, const float* U, const float* P, const float* bp, void* out, float* attn,
                               int32_t B, int32_t xb, int32_t T, int32_t C, int32_t heads, void* stream) {
   if (!x || !U || !P || !out || !attn || B <= 0 || xb <= 0 || B % xb || T <= 0) return CAVP_ERR_BAD_ARG;
-  if ((dtype != CAVP_F32 && dtype != CAVP_BF16) || !ok_shape(C, heads)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype) || !ok_shape(C, heads)) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(out) || !al16(U) || !al16(P) || (bp && !al16(bp))) return CAVP_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(token_groups(T, B, 4096), B);   // four waves per SIMD
-  if (dtype == CAVP_F32)
-    attn1_fwd_kernel<float, 4><<<grid, 256, 0, s>>>((const float*)x, U, P, bp, (float*)out, attn, xb, T, C);
-  else
-    attn1_fwd_kernel<bf16_t, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, U, P, bp, (bf16_t*)out, attn, xb, T, C);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+    attn1_fwd_kernel<E, 4><<<grid, 256, 0, s>>>((const E*)x, U, P, bp, (E*)out, attn, xb, T, C); });
+  CHECK_LAUNCH();
 }
 
 extern "C" size_t cavp_attn1_bwd_workspace_bytes(int32_t B, int32_t xb, int32_t T, int32_t C, int32_t heads) {
@@ -486,7 +482,7 @@ extern "C" int cavp_attn1_bwd(int32_t dtype, const void* dout, const void* x, co
                               float* dP, float* dbp, void* workspace, size_t workspace_bytes, int32_t B, int32_t xb, int32_t T, int32_t C,
                               int32_t heads, void* stream) {
   if (!dout || !x || !U || !P || !dx || !dU || !dP || !workspace || B <= 0 || xb <= 0 || B % xb || T <= 0) return CAVP_ERR_BAD_ARG;
-  if ((dtype != CAVP_F32 && dtype != CAVP_BF16) || !ok_shape(C, heads)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype) || !ok_shape(C, heads)) return CAVP_ERR_UNSUPPORTED;
   if (!al16(dout) || !al16(x) || !al16(dx) || !al16(U) || !al16(P) || !al16(workspace)) return CAVP_ERR_ALIGN;
   if (workspace_bytes < cavp_attn1_bwd_workspace_bytes(B, xb, T, C, heads)) return CAVP_ERR_WORKSPACE;
   const int g = token_groups(T, xb);
@@ -502,31 +498,27 @@ extern "C" int cavp_attn1_bwd(int32_t dtype, const void* dout, const void* x, co
     (void)hipFuncSetAttribute((const void*)attn1_bwd_kernel<bf16_t, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 4 * 512 * 4);
     attr = true;
   }
-  if (dtype == CAVP_F32)
-    attn1_bwd_kernel<float, 4><<<grid, 256, lds, s>>>((const float*)dout, (const float*)x, U, P, (float*)dx, slabU, slabP, slabB, B, xb, T, C);
-  else
-    attn1_bwd_kernel<bf16_t, 4><<<grid, 256, lds, s>>>((const bf16_t*)dout, (const bf16_t*)x, U, P, (bf16_t*)dx, slabU, slabP, slabB, B, xb, T, C);
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+    attn1_bwd_kernel<E, 4><<<grid, 256, lds, s>>>((const E*)dout, (const E*)x, U, P, (E*)dx, slabU, slabP, slabB, B, xb, T, C); });
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   int nb = (2 * B * heads * C + 255) / 256;
   if (nb > 1024) nb = 1024;
   const int nb_b = (C + 3) / 4;
   attn1_slabsum_kernel<<<nb + nb_b, 256, 0, s>>>(slabU, slabP, slabB, dU, dP, dbp, B, xb, g, heads * C, C, nb);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_attn1_finish(int32_t dtype, const float* wq, const float* wp, const void* k, const void* v, const float* dU,
                                  const float* dP, float* dwq, float* dwp, float* dk, float* dv, int32_t B, int32_t C, int32_t heads,
                                  float scale, void* stream) {
   if (!wq || !wp || !k || !v || !dU || !dP || !dwq || !dwp || !dk || !dv || B <= 0) return CAVP_ERR_BAD_ARG;
-  if ((dtype != CAVP_F32 && dtype != CAVP_BF16) || !ok_shape(C, heads) || B * heads > 8192) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype) || !ok_shape(C, heads) || B * heads > 8192) return CAVP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   size_t lds = (size_t)2 * C + 3 * (size_t)(C / heads);
   if ((size_t)B * heads > lds) lds = (size_t)B * heads;
   lds *= sizeof(float);
   const int grid = 2 * C + B * heads;
-  if (dtype == CAVP_F32)
-    attn1_finish_kernel<float><<<grid, 256, lds, s>>>(wq, wp, (const float*)k, (const float*)v, dU, dP, dwq, dwp, dk, dv, B, C, heads, scale);
-  else
-    attn1_finish_kernel<bf16_t><<<grid, 256, lds, s>>>(wq, wp, (const bf16_t*)k, (const bf16_t*)v, dU, dP, dwq, dwp, dk, dv, B, C, heads, scale);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using E = decltype(t);
+    attn1_finish_kernel<E><<<grid, 256, lds, s>>>(wq, wp, (const E*)k, (const E*)v, dU, dP, dwq, dwp, dk, dv, B, C, heads, scale); });
+  CHECK_LAUNCH();
 }

@@ -9,6 +9,7 @@
 //   4. symm_add:        G = dS + dS^T  (anchors and contrasts are the same tensor: both roles get gradient)
 //   5. dA = G A (cavp_conv2d_wgrad_nhwc), then l2norm_bwd_scatter back into the NHWC feature gradient
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -399,7 +400,6 @@ __global__ __launch_bounds__(256) void l2norm_bwd_scatter_dev_kernel(const float
 }
 
 }  // namespace
-#define CHECK_LAUNCH() return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH
 
 // F.interpolate(mode='nearest') of the label maps to the feature resolution (contrastive_aud.py:18-22): source index
 // min(floor(dst * float32(in / out)), in - 1) per axis, as ATen computes it.  int64 [B][H][W] -> int32 [B][h][w].
@@ -423,7 +423,7 @@ extern "C" int cavp_label_nearest(const int64_t* gt, int32_t* out, int32_t B, in
   if (nb > 4096) nb = 4096;
   label_nearest_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>((const long long*)gt, out, B, H, W, h, w, (float)H / (float)h,
                                                                  (float)W / (float)w);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_gather_l2norm(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_p,

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "igemm_params.h"
+#include "host_util.h"
 
 // Shared epilogue math for one output element.
 __device__ __forceinline__ float epi_one(float v, int cc, int n_img, const IgemmParams& p) {
@@ -1086,8 +1087,8 @@ Plan make_plan(const cavp_conv_desc* d_in, bool allow_big = true, bool allow_par
     pl.status = CAVP_ERR_BAD_ARG;
     return pl;
   }
-  if (d->dtype != CAVP_F32 && d->dtype != CAVP_BF16) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
-  const int VE = d->dtype == CAVP_F32 ? 4 : 8;
+  if (!dt_ok(d->dtype)) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
+  const int VE = dt_ve(d->dtype);
   if (d->Cin % VE || d->ldx % VE) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
   if (d->KH * d->KW > 9) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
   IgemmParams& p = pl.p;
@@ -1315,7 +1316,7 @@ static int tail_split_images(const cavp_conv_desc* d, const Plan& pl, bool with_
 extern "C" int cavp_conv2d_tile_stats_layout(const cavp_conv_desc* d, int32_t* tiles, int32_t* rows_per_tile) {
   Plan pl = make_plan(d);
   if (pl.status != CAVP_OK || !tiles || !rows_per_tile) return 0;
-  const int VE = d->dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(d->dtype);
   if (pl.p.splitk != 1 || pl.direct_epi || d->Cout % VE || d->ldy % VE) return 0;
   int BP = 0;
   for (int i = 0; i < kNumTiles; ++i)
@@ -1390,8 +1391,8 @@ extern "C" int cavp_conv2d_nhwc_bnbwd(const cavp_conv_desc* d, const void* x, co
     return CAVP_ERR_BAD_ARG;
   if (b->act != CAVP_ACT_NONE && b->act != CAVP_ACT_RELU && b->act != CAVP_ACT_LEAKY) return CAVP_ERR_UNSUPPORTED;
   if (!b->out && b->act != CAVP_ACT_NONE && (!b->fwd_scale || !b->fwd_shift)) return CAVP_ERR_BAD_ARG;
-  const int VE = d->dtype == CAVP_F32 ? 4 : 8;
-  if (b->ld_z < d->Cout || b->ld_z % VE || !aligned(b->z, 16) || (b->out && (b->ld_out < d->Cout || b->ld_out % VE || !aligned(b->out, 16))))
+  const int VE = dt_ve(d->dtype);
+  if (b->ld_z < d->Cout || b->ld_z % VE || !al16(b->z) || (b->out && (b->ld_out < d->Cout || b->ld_out % VE || !al16(b->out))))
     return CAVP_ERR_ALIGN;
   int32_t tiles = 0, rpt = 0;
   if (!cavp_conv2d_bnbwd_layout(d, &tiles, &rpt)) return CAVP_ERR_UNSUPPORTED;
@@ -1414,10 +1415,10 @@ static int conv2d_launch(const cavp_conv_desc* d, const void* x, const void* w, 
   const bool par_ok = !(tile_stats || nbias || aux || fused);
   Plan pl = make_plan(d, true, par_ok);
   if (pl.status != CAVP_OK) return pl.status;
-  if (!aligned(x, 16) || !aligned(w, 16)) return CAVP_ERR_ALIGN;
+  if (!al16(x) || !al16(w)) return CAVP_ERR_ALIGN;
   if (tile_is_big(pl.tile_id) && d->tile % 100 == 0 &&
-      !(aligned(y, 16) && (!residual || aligned(residual, 16)) && (!scale || aligned(scale, 16)) && (!shift || aligned(shift, 16)) &&
-        (!nbias || aligned(nbias, 16)))) {
+      !(al16(y) && (!residual || al16(residual)) && (!scale || al16(scale)) && (!shift || al16(shift)) &&
+        (!nbias || al16(nbias)))) {
     if (tile_stats) return CAVP_ERR_ALIGN;   // the statistics layout was sized for the 256x256 tile
     pl = make_plan(d, false, par_ok);        // automatically chosen big tile, but an operand is not 16-byte aligned
     if (pl.status != CAVP_OK) return pl.status;
@@ -1443,7 +1444,7 @@ static int conv2d_launch(const cavp_conv_desc* d, const void* x, const void* w, 
                            tile_stats ? tile_stats + (opix / 128) * (size_t)d->Cout * 2 : nullptr, stream, false);
     }
   }
-  if (pl.ws_bytes > 0 && (!workspace || workspace_bytes < pl.ws_bytes || !aligned(workspace, 16)))
+  if (pl.ws_bytes > 0 && (!workspace || workspace_bytes < pl.ws_bytes || !al16(workspace)))
     return CAVP_ERR_WORKSPACE;
   IgemmParams& p = pl.p;
   p.x = x; p.w = w; p.y = y; p.scale = scale; p.shift = shift; p.nbias = nbias; p.res = residual;
@@ -1457,12 +1458,12 @@ static int conv2d_launch(const cavp_conv_desc* d, const void* x, const void* w, 
     p.w_bytes = (int)wb;
   }
   p.vec_io = (d->Cout % 4 == 0) && (d->ldy % 4 == 0) && aligned(y, 4 * es) &&
-             (!residual || (d->ldr % 4 == 0 && aligned(residual, 4 * es))) && (!scale || aligned(scale, 16)) &&
-             (!shift || aligned(shift, 16)) && (!nbias || aligned(nbias, 16));
-  const int VE = d->dtype == CAVP_F32 ? 4 : 8;
-  p.coalesced = !pl.direct_epi && p.splitk == 1 && (d->Cout % VE == 0) && (d->ldy % VE == 0) && aligned(y, 16) &&
-                (!residual || (d->ldr % VE == 0 && aligned(residual, 16))) && (!scale || aligned(scale, 16)) &&
-                (!shift || aligned(shift, 16));
+             (!residual || (d->ldr % 4 == 0 && aligned(residual, 4 * es))) && (!scale || al16(scale)) &&
+             (!shift || al16(shift)) && (!nbias || al16(nbias));
+  const int VE = dt_ve(d->dtype);
+  p.coalesced = !pl.direct_epi && p.splitk == 1 && (d->Cout % VE == 0) && (d->ldy % VE == 0) && al16(y) &&
+                (!residual || (d->ldr % VE == 0 && al16(residual))) && (!scale || al16(scale)) &&
+                (!shift || al16(shift));
   p.tile_stats = tile_stats;
   if (bnb) {
     if (!p.coalesced || !tile_has_bnb(pl.tile_id)) return CAVP_ERR_UNSUPPORTED;   // see cavp_conv2d_bnbwd_layout
@@ -1471,25 +1472,23 @@ static int conv2d_launch(const cavp_conv_desc* d, const void* x, const void* w, 
     p.bnb_act = bnb->act; p.bnb_part = bnb->partials;
   }
   p.aux = aux; p.aux_mode = d->aux_mode; p.ld_aux = d->ld_aux; p.res_rows = residual ? d->res_rows : 0;
-  if (fused && !(p.coalesced && (!aux || (d->ld_aux % VE == 0 && aligned(aux, 16))))) return CAVP_ERR_UNSUPPORTED;
+  if (fused && !(p.coalesced && (!aux || (d->ld_aux % VE == 0 && al16(aux))))) return CAVP_ERR_UNSUPPORTED;
   if (p.res_rows > 0 && (long long)p.res_rows > p.M) return CAVP_ERR_BAD_ARG;
   if (tile_stats && !p.coalesced) return CAVP_ERR_UNSUPPORTED;   // see cavp_conv2d_tile_stats_layout
   if (tile_is_big(pl.tile_id) && !p.coalesced) return CAVP_ERR_ALIGN;   // the 256x256 tile only has the 16-byte epilogue
   hipStream_t s = (hipStream_t)stream;
   const bool upm = p.up_mask != 0;
-  hipError_t e = d->dtype == CAVP_F32
-                     ? (upm ? launch_tile<float, true>(pl.tile_id, p, pl.nblk, s) : launch_tile<float, false>(pl.tile_id, p, pl.nblk, s))
-                     : (upm ? launch_tile<bf16_t, true>(pl.tile_id, p, pl.nblk, s) : launch_tile<bf16_t, false>(pl.tile_id, p, pl.nblk, s));
+  hipError_t e = hipSuccess;
+  cavp_dispatch_dtype(d->dtype, [&](auto t) { using T = decltype(t);
+    e = upm ? launch_tile<T, true>(pl.tile_id, p, pl.nblk, s) : launch_tile<T, false>(pl.tile_id, p, pl.nblk, s); });
   if (e != hipSuccess) return CAVP_ERR_LAUNCH;
   if (p.splitk > 1) {
     const long long total = (long long)p.M * ((p.Cout + 3) / 4);
     int nb = (int)((total + 255) / 256);
     if (nb > 4096) nb = 4096;
-    if (d->dtype == CAVP_F32)
-      splitk_epilogue_kernel<float><<<dim3(nb), dim3(256), 0, s>>>(p);
-    else
-      splitk_epilogue_kernel<bf16_t><<<dim3(nb), dim3(256), 0, s>>>(p);
-    if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    cavp_dispatch_dtype(d->dtype, [&](auto t) { using T = decltype(t);
+      splitk_epilogue_kernel<T><<<dim3(nb), dim3(256), 0, s>>>(p); });
+    CHECK_LAUNCH();
   }
   return CAVP_OK;
 }

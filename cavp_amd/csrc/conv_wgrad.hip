@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "wgrad_params.h"
+#include "host_util.h"
 
 // One logical workgroup `bid` of one weight gradient (shared by the single and the grouped launch).
 // BK = pixel rows per stage; BIAS: also the bias gradient (column sums of dY); NSTG = LDS stages: 2 (BK = 32: four 32 KiB
@@ -509,7 +510,7 @@ WgradPlan make_wgrad_plan(const cavp_conv_desc* d, int force_ks = 0, bool big = 
   pl.status = CAVP_OK;
   if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 ||
       d->dil <= 0 || d->pad < 0 || d->ldx < d->Cin || d->ldy < d->Cout) { pl.status = CAVP_ERR_BAD_ARG; return pl; }
-  if (d->dtype != CAVP_F32 && d->dtype != CAVP_BF16) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
+  if (!dt_ok(d->dtype)) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
   const int es = d->dtype == CAVP_F32 ? 4 : 2;
   const int VE = 16 / es;
   if (d->Cin % VE || d->Cout % VE || d->ldx % VE || d->ldy % VE || d->KH * d->KW > 9) { pl.status = CAVP_ERR_UNSUPPORTED; return pl; }
@@ -585,6 +586,42 @@ WgradPlan make_wgrad_plan(const cavp_conv_desc* d, int force_ks = 0, bool big = 
   pl.ws_bytes = ks > 1 ? ((size_t)ks * d->Cout * p.ntaps_all * d->Cin + (size_t)ks * d->Cout) * sizeof(float) : 0;   // dW slabs + bias slabs
   return pl;
 }
+
+// Binds one planned job to its tensors: pointers, layout / overwrite flags, the bias slabs behind the dW slabs, the debug knob.
+// pl.nblk == 0 (every tap is outside the image: the gradient is zero) leaves nothing to launch: the caller skips the job on
+// CAVP_OK.  ws_ok: the caller's workspace holds this job's slabs (reported after a misaligned tensor, before any clear).
+int bind_wgrad_job(WgradPlan& pl, const cavp_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias, float* slabs,
+                   bool ws_ok, hipStream_t s) {
+  const size_t dw_bytes = (size_t)d->Cout * d->KH * d->KW * d->Cin * sizeof(float);
+  if (pl.nblk == 0) return d->dw_overwrite && cavp_zero_f32_async(dw, dw_bytes, s) != hipSuccess ? CAVP_ERR_LAUNCH : CAVP_OK;
+  if (!al16(x) || !al16(dy) || !al16(dw)) return CAVP_ERR_ALIGN;
+  if (!ws_ok) return CAVP_ERR_WORKSPACE;
+  WgradParams& p = pl.p;
+  p.x = x; p.dy = dy; p.dw = dw; p.slabs = slabs; p.dbias = dbias;
+  p.oihw = d->dw_oihw != 0 && p.ntaps_all > 1;   // (1x1: the two layouts coincide)
+  p.overwrite = d->dw_overwrite != 0;
+  if (p.overwrite && p.ntaps < p.ntaps_all) {   // dead taps of a dilated kernel are never visited: clear, then accumulate
+    if (cavp_zero_f32_async(dw, dw_bytes, s) != hipSuccess) return CAVP_ERR_LAUNCH;
+    p.overwrite = 0;
+  }
+  p.bias_slabs = p.slabs ? p.slabs + (size_t)p.ksplit * d->Cout * p.ntaps_all * d->Cin : nullptr;
+  static const int dbg = cavp_knob_int("CAVP_WGRAD_DBG", 0);   // (profile builds; the 256 x 256 tile reads bits 1 and 2)
+  p.dbg = dbg;
+  return CAVP_OK;
+}
+
+// slab reduce of a split job: split groups per workgroup (the split dimension is spread when there are few output quads) and
+// workgroups, at most `cap`
+int wgrad_reduce_geometry(const WgradParams& p, int cap, int* zgrp, int* blocks) {
+  const long long quads = (long long)p.Cout * p.ntaps * (p.Cin / 4);
+  if (quads > 0x7fffffffll) return CAVP_ERR_UNSUPPORTED;
+  int zg = 1;
+  while (zg < 16 && zg * 2 <= p.ksplit && quads * zg < 131072) zg *= 2;
+  const long long nb = (quads + (256 / zg) - 1) / (256 / zg);
+  *zgrp = zg;
+  *blocks = nb > cap ? cap : (int)nb;
+  return CAVP_OK;
+}
 }  // namespace
 
 extern "C" size_t cavp_conv2d_wgrad_workspace_bytes(const cavp_conv_desc* d) {
@@ -607,29 +644,13 @@ extern "C" int cavp_conv2d_wgrad_nhwc(const cavp_conv_desc* d, const void* x, co
   }
   WgradPlan pl = make_wgrad_plan(d);
   if (pl.status != CAVP_OK) return pl.status;
-  const size_t dw_bytes = (size_t)d->Cout * d->KH * d->KW * d->Cin * sizeof(float);
-  if (pl.nblk == 0) {   // every tap is outside the image: the gradient is zero
-    if (d->dw_overwrite && cavp_zero_f32_async(dw, dw_bytes, (hipStream_t)stream) != hipSuccess) return CAVP_ERR_LAUNCH;
-    return CAVP_OK;
-  }
-  if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || ((uintptr_t)dw & 15)) return CAVP_ERR_ALIGN;
-  if (pl.ws_bytes > 0 && (!workspace || workspace_bytes < pl.ws_bytes || ((uintptr_t)workspace & 15))) return CAVP_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const bool ws_ok = pl.ws_bytes == 0 || (workspace && workspace_bytes >= pl.ws_bytes && al16(workspace));
+  const int st = bind_wgrad_job(pl, d, x, dy, dw, dbias, (float*)workspace, ws_ok, s);
+  if (st != CAVP_OK || pl.nblk == 0) return st;
   WgradParams& p = pl.p;
-  p.x = x; p.dy = dy; p.dw = dw; p.slabs = (float*)workspace; p.dbias = dbias;
-  p.oihw = d->dw_oihw != 0 && p.ntaps_all > 1;   // (1x1: the two layouts coincide)
-  p.overwrite = d->dw_overwrite != 0;
-  if (p.overwrite && p.ntaps < p.ntaps_all) {   // dead taps of a dilated kernel are never visited: clear, then accumulate
-    if (cavp_zero_f32_async(dw, dw_bytes, (hipStream_t)stream) != hipSuccess) return CAVP_ERR_LAUNCH;
-    p.overwrite = 0;
-  }
-  p.bias_slabs = p.slabs ? p.slabs + (size_t)p.ksplit * d->Cout * p.ntaps_all * d->Cin : nullptr;
-  {
-    static const int dbg = cavp_knob_int("CAVP_WGRAD_DBG", 0);
-    p.dbg = dbg;
-  }
   static const int bk = cavp_knob_int("CAVP_WGRAD_BK", 32);   // A/B knob (profiling)
   const int lds = 2 * 2 * bk * 256;
-  hipStream_t s = (hipStream_t)stream;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)wgrad_kernel<float, 64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 64 * 256);
@@ -640,30 +661,22 @@ extern "C" int cavp_conv2d_wgrad_nhwc(const cavp_conv_desc* d, const void* x, co
   }
 #define WG_LAUNCH(T, B, BI) wgrad_kernel<T, B, BI><<<pl.nblk, 256, lds, s>>>(p)
   const bool bi = dbias != nullptr;
-  if (d->dtype == CAVP_F32) {
-    if (bk == 32) { if (bi) WG_LAUNCH(float, 32, true); else WG_LAUNCH(float, 32, false); }
-    else { if (bi) WG_LAUNCH(float, 64, true); else WG_LAUNCH(float, 64, false); }
-  } else {
-    if (bk == 32) { if (bi) WG_LAUNCH(bf16_t, 32, true); else WG_LAUNCH(bf16_t, 32, false); }
-    else { if (bi) WG_LAUNCH(bf16_t, 64, true); else WG_LAUNCH(bf16_t, 64, false); }
-  }
+  cavp_dispatch_dtype(d->dtype, [&](auto t) { using T = decltype(t);
+    if (bk == 32) { if (bi) WG_LAUNCH(T, 32, true); else WG_LAUNCH(T, 32, false); }
+    else { if (bi) WG_LAUNCH(T, 64, true); else WG_LAUNCH(T, 64, false); } });
 #undef WG_LAUNCH
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   if (p.ksplit > 1) {
-    const long long quads = (long long)p.Cout * p.ntaps * (p.Cin / 4);
-    if (quads > 0x7fffffffll) return CAVP_ERR_UNSUPPORTED;
-    int zgrp = 1;   // split groups per workgroup: spread the split dimension when there are few output quads
-    while (zgrp < 16 && zgrp * 2 <= p.ksplit && quads * zgrp < 131072) zgrp *= 2;
-    long long nb = (quads + (256 / zgrp) - 1) / (256 / zgrp);
-    if (nb > 8192) nb = 8192;
+    int zgrp, nb;
+    if (wgrad_reduce_geometry(p, 8192, &zgrp, &nb) != CAVP_OK) return CAVP_ERR_UNSUPPORTED;
     switch (zgrp) {
-      case 1: wgrad_reduce_kernel<1><<<(int)nb, 256, 0, s>>>(p); break;
-      case 2: wgrad_reduce_kernel<2><<<(int)nb, 256, 0, s>>>(p); break;
-      case 4: wgrad_reduce_kernel<4><<<(int)nb, 256, 0, s>>>(p); break;
-      case 8: wgrad_reduce_kernel<8><<<(int)nb, 256, 0, s>>>(p); break;
-      default: wgrad_reduce_kernel<16><<<(int)nb, 256, 0, s>>>(p); break;
+      case 1: wgrad_reduce_kernel<1><<<nb, 256, 0, s>>>(p); break;
+      case 2: wgrad_reduce_kernel<2><<<nb, 256, 0, s>>>(p); break;
+      case 4: wgrad_reduce_kernel<4><<<nb, 256, 0, s>>>(p); break;
+      case 8: wgrad_reduce_kernel<8><<<nb, 256, 0, s>>>(p); break;
+      default: wgrad_reduce_kernel<16><<<nb, 256, 0, s>>>(p); break;
     }
-    if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    CHECK_LAUNCH();
   }
   return CAVP_OK;
 }
@@ -782,7 +795,7 @@ extern "C" int cavp_conv2d_wgrad_group(const cavp_wgrad_job* jobs, int32_t njobs
                                        void* stream) {
   GroupPlan gp = make_group_plan(jobs, njobs);
   if (gp.status != CAVP_OK) return gp.status;
-  if (gp.ws_bytes > 0 && (!workspace || workspace_bytes < gp.ws_bytes || ((uintptr_t)workspace & 15))) return CAVP_ERR_WORKSPACE;
+  if (gp.ws_bytes > 0 && (!workspace || workspace_bytes < gp.ws_bytes || !al16(workspace))) return CAVP_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   // three kernel-argument blocks: the jobs of the 128 x 128 tile, the jobs of the 256 x 256 tile, and ALL jobs that split their
   // pixel range for the one grouped slab reduce (only its red_end / red_zg / job fields are read there)
@@ -791,41 +804,20 @@ extern "C" int cavp_conv2d_wgrad_group(const cavp_wgrad_job* jobs, int32_t njobs
   bool sbias = false, bbias = false;
   for (int j = 0; j < njobs; ++j) {
     const cavp_wgrad_job& jb = jobs[j];
-    const cavp_conv_desc* d = &jb.desc;
     if (!jb.x || !jb.dy || !jb.dw) return CAVP_ERR_BAD_ARG;
     for (int i = 0; i < j; ++i)   // two jobs adding into one gradient would race inside the launch
       if (jobs[i].dw == jb.dw || (jb.dbias && jobs[i].dbias == jb.dbias)) return CAVP_ERR_BAD_ARG;
     WgradPlan& pl = gp.pl[j];
-    const size_t dw_bytes = (size_t)d->Cout * d->KH * d->KW * d->Cin * sizeof(float);
-    if (pl.nblk == 0) {   // every tap is outside the image: the gradient is zero
-      if (d->dw_overwrite && cavp_zero_f32_async(jb.dw, dw_bytes, s) != hipSuccess) return CAVP_ERR_LAUNCH;
-      continue;
-    }
-    if (((uintptr_t)jb.x & 15) || ((uintptr_t)jb.dy & 15) || ((uintptr_t)jb.dw & 15)) return CAVP_ERR_ALIGN;
+    float* slabs = pl.ws_bytes ? (float*)((char*)workspace + gp.slab_off[j]) : nullptr;   // (the group's workspace was checked above)
+    const int st = bind_wgrad_job(pl, &jb.desc, jb.x, jb.dy, jb.dw, jb.dbias, slabs, true, s);
+    if (st != CAVP_OK) return st;
+    if (pl.nblk == 0) continue;
     WgradParams& p = pl.p;
-    p.x = jb.x; p.dy = jb.dy; p.dw = jb.dw; p.dbias = jb.dbias;
-    p.slabs = pl.ws_bytes ? (float*)((char*)workspace + gp.slab_off[j]) : nullptr;
-    p.oihw = d->dw_oihw != 0 && p.ntaps_all > 1;
-    p.overwrite = d->dw_overwrite != 0;
-    if (p.overwrite && p.ntaps < p.ntaps_all) {   // dead taps of a dilated kernel are never visited: clear, then accumulate
-      if (cavp_zero_f32_async(jb.dw, dw_bytes, s) != hipSuccess) return CAVP_ERR_LAUNCH;
-      p.overwrite = 0;
-    }
-    p.bias_slabs = p.slabs ? p.slabs + (size_t)p.ksplit * d->Cout * p.ntaps_all * d->Cin : nullptr;
-    {
-      static const int dbg = cavp_knob_int("CAVP_WGRAD_DBG", 0);   // (profile builds; the 256 x 256 tile reads bits 1 and 2)
-      p.dbg = dbg;
-    }
     p.red_zg = 1;
     if (p.ksplit > 1) {
-      const long long quads = (long long)p.Cout * p.ntaps * (p.Cin / 4);
-      if (quads > 0x7fffffffll) return CAVP_ERR_UNSUPPORTED;
-      int zgrp = 1;
-      while (zgrp < 16 && zgrp * 2 <= p.ksplit && quads * zgrp < 131072) zgrp *= 2;
-      long long nbk = (quads + (256 / zgrp) - 1) / (256 / zgrp);
-      if (nbk > 2048) nbk = 2048;
-      p.red_zg = zgrp;
-      rblocks += (int)nbk;
+      int nbk;
+      if (wgrad_reduce_geometry(p, 2048, &p.red_zg, &nbk) != CAVP_OK) return CAVP_ERR_UNSUPPORTED;
+      rblocks += nbk;
       gr.job[nr] = p;
       gr.red_end[nr] = rblocks;
       ++nr;
@@ -850,19 +842,14 @@ extern "C" int cavp_conv2d_wgrad_group(const cavp_wgrad_job* jobs, int32_t njobs
   }
   if (ns > 0) {
     const int lds = 2 * 2 * 32 * 256;
-    const bool f32 = jobs[0].desc.dtype == CAVP_F32;
-    if (f32) {
-      if (sbias) wgrad_group_kernel<float, true><<<sblocks, 256, lds, s>>>(gs);
-      else wgrad_group_kernel<float, false><<<sblocks, 256, lds, s>>>(gs);
-    } else {
-      if (sbias) wgrad_group_kernel<bf16_t, true><<<sblocks, 256, lds, s>>>(gs);
-      else wgrad_group_kernel<bf16_t, false><<<sblocks, 256, lds, s>>>(gs);
-    }
-    if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    cavp_dispatch_dtype(jobs[0].desc.dtype, [&](auto t) { using T = decltype(t);
+      if (sbias) wgrad_group_kernel<T, true><<<sblocks, 256, lds, s>>>(gs);
+      else wgrad_group_kernel<T, false><<<sblocks, 256, lds, s>>>(gs); });
+    if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   }
   if (nr > 0) {
     wgrad_reduce_group_kernel<<<rblocks, 256, 0, s>>>(gr);
-    if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    CHECK_LAUNCH();
   }
   return CAVP_OK;
 }

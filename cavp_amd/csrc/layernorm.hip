@@ -11,6 +11,7 @@
 // * backward: dgamma / dbeta are accumulated in registers over the workgroup's rows, combined across the row groups of
 //   the wave by shuffles, across the 4 waves through LDS, and leave as one f32 atomic per channel per workgroup.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -254,9 +255,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const T* __restr
   }
 }
 
-inline bool dt_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // (G, PLV) for C channels of VE-element vectors; 0 if C is too wide
 inline bool ln_geometry(int C, int VE, int* G, int* PLV) {
   const int vecs = (C + VE - 1) / VE;
@@ -276,7 +274,9 @@ inline bool ln_geometry(int C, int VE, int* G, int* PLV) {
 
 }  // namespace
 
-#define LN_DISPATCH(KERNEL_CALL)                                                     \
+// the (G, PLV) instantiations of ln_geometry; `st` gets the status of a geometry that has none.  bf16 stops at 3 vectors per
+// lane: 5 would need an 80 KiB LDS partial array in the backward; C <= 1536 covers every norm layer
+#define LN_DISPATCH(T, KERNEL_CALL)                                                  \
   switch (G * 10 + PLV) {                                                            \
     case 81: KERNEL_CALL(8, 1); break;                                               \
     case 161: KERNEL_CALL(16, 1); break;                                             \
@@ -285,21 +285,10 @@ inline bool ln_geometry(int C, int VE, int* G, int* PLV) {
     case 641: KERNEL_CALL(64, 1); break;                                             \
     case 642: KERNEL_CALL(64, 2); break;                                             \
     case 643: KERNEL_CALL(64, 3); break;                                             \
-    case 645: KERNEL_CALL(64, 5); break;                                             \
-    default: return CAVP_ERR_UNSUPPORTED;                                            \
-  }
-
-// bf16: 5 vectors per lane would need an 80 KiB LDS partial array in the backward; C <= 1536 covers every norm layer
-#define LN_DISPATCH_BF16(KERNEL_CALL)                                                \
-  switch (G * 10 + PLV) {                                                            \
-    case 81: KERNEL_CALL(8, 1); break;                                               \
-    case 161: KERNEL_CALL(16, 1); break;                                             \
-    case 163: KERNEL_CALL(16, 3); break;                                             \
-    case 321: KERNEL_CALL(32, 1); break;                                             \
-    case 641: KERNEL_CALL(64, 1); break;                                             \
-    case 642: KERNEL_CALL(64, 2); break;                                             \
-    case 643: KERNEL_CALL(64, 3); break;                                             \
-    default: return CAVP_ERR_UNSUPPORTED;                                            \
+    case 645:                                                                        \
+      if constexpr (sizeof(T) == 4) { KERNEL_CALL(64, 5); break; }                   \
+      [[fallthrough]];                                                               \
+    default: st = CAVP_ERR_UNSUPPORTED;                                              \
   }
 
 extern "C" int cavp_layernorm(int32_t dtype, const void* x, const float* gamma, const float* beta, void* y,
@@ -313,7 +302,7 @@ extern "C" int cavp_layernorm_residual(int32_t dtype, const void* x, const void*
   if (!x || !gamma || !beta || !y || rows <= 0 || C <= 0 || ldx < C || ldy < C) return CAVP_ERR_BAD_ARG;
   if (branch && (!row_scale || !y_sum || rows_per_group <= 0 || rows % rows_per_group)) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE || ldy % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(y) || !al16(gamma) || !al16(beta) || !al16(branch) || !al16(y_sum)) return CAVP_ERR_ALIGN;
   int G, PLV;
@@ -323,16 +312,14 @@ extern "C" int cavp_layernorm_residual(int32_t dtype, const void* x, const void*
   if (nbl > 8192) nbl = 8192;
   const int nb = (int)nbl;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32) {
-#define CALL(g, p) layernorm_vec_kernel<float, g, p><<<nb, 256, 0, s>>>((const float*)x, gamma, beta, (float*)y, rows, C, ldx, ldy, eps, (const float*)branch, row_scale, rows_per_group, (float*)y_sum)
-    LN_DISPATCH(CALL)
+  int st = CAVP_OK;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+#define CALL(g, p) layernorm_vec_kernel<T, g, p><<<nb, 256, 0, s>>>((const T*)x, gamma, beta, (T*)y, rows, C, ldx, ldy, eps, (const T*)branch, row_scale, rows_per_group, (T*)y_sum)
+    LN_DISPATCH(T, CALL)
 #undef CALL
-  } else {
-#define CALL(g, p) layernorm_vec_kernel<bf16_t, g, p><<<nb, 256, 0, s>>>((const bf16_t*)x, gamma, beta, (bf16_t*)y, rows, C, ldx, ldy, eps, (const bf16_t*)branch, row_scale, rows_per_group, (bf16_t*)y_sum)
-    LN_DISPATCH_BF16(CALL)
-#undef CALL
-  }
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  });
+  if (st != CAVP_OK) return st;
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_layernorm_bwd(int32_t dtype, const void* dy, const void* x, const float* gamma, void* dx,
@@ -350,7 +337,7 @@ extern "C" int cavp_layernorm_bwd_add(int32_t dtype, const void* dy, const void*
   if (!al16(dx_scaled)) return CAVP_ERR_ALIGN;
   if (!dy || !x || !gamma || !dx || !dgamma || !dbeta || rows <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ld_dy % VE || ld_x % VE || ld_dx % VE || (dx_add && ld_add % VE)) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(dy) || !al16(dx) || !al16(gamma) || !al16(dx_add)) return CAVP_ERR_ALIGN;
   int G, PLV;
@@ -368,16 +355,14 @@ extern "C" int cavp_layernorm_bwd_add(int32_t dtype, const void* dy, const void*
   bool det_err;
   float* det = cavp_det_scratch(gx, C, &det_err);
   if (det_err) return CAVP_ERR_WORKSPACE;
-  if (dtype == CAVP_F32) {
-#define CALL(g, p) layernorm_bwd_vec_kernel<float, g, p><<<gx, 256, 0, s>>>((const float*)dy, (const float*)x, gamma, (float*)dx, dgamma, dbeta, rows, C, ld_dy, ld_x, ld_dx, eps, rpb, det, (const float*)dx_add, ld_add, (float*)dx_scaled, row_scale, rows_per_group)
-    LN_DISPATCH(CALL)
+  int st = CAVP_OK;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+#define CALL(g, p) layernorm_bwd_vec_kernel<T, g, p><<<gx, 256, 0, s>>>((const T*)dy, (const T*)x, gamma, (T*)dx, dgamma, dbeta, rows, C, ld_dy, ld_x, ld_dx, eps, rpb, det, (const T*)dx_add, ld_add, (T*)dx_scaled, row_scale, rows_per_group)
+    LN_DISPATCH(T, CALL)
 #undef CALL
-  } else {
-#define CALL(g, p) layernorm_bwd_vec_kernel<bf16_t, g, p><<<gx, 256, 0, s>>>((const bf16_t*)dy, (const bf16_t*)x, gamma, (bf16_t*)dx, dgamma, dbeta, rows, C, ld_dy, ld_x, ld_dx, eps, rpb, det, (const bf16_t*)dx_add, ld_add, (bf16_t*)dx_scaled, row_scale, rows_per_group)
-    LN_DISPATCH_BF16(CALL)
-#undef CALL
-  }
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+  });
+  if (st != CAVP_OK) return st;
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   if (det && cavp_det_finish(det, gx, C, dgamma, dbeta, s) != hipSuccess) return CAVP_ERR_LAUNCH;
   return CAVP_OK;
 }

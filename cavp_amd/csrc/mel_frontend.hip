@@ -9,6 +9,7 @@
 // bin: 322 us for 64 clips; this one: see profiles/r01_notes.md.)
 // Output is the [N][1][frames][mels] f32 tensor the audio encoder eats.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -71,5 +72,5 @@ extern "C" int cavp_mel_frontend(const float* wave, int32_t N, int32_t A, const 
   if (n_frames > 1 + A / hop) return CAVP_ERR_BAD_ARG;   // torch.stft(center=True) yields 1 + A / hop frames
   mel_frontend_kernel<<<dim3(n_frames, N), 256, 0, (hipStream_t)stream>>>(wave, window, fb, out, A, hop, n_frames, n_mels, amin,
                                                                          spec_min, 1.f / (spec_max - spec_min));
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }

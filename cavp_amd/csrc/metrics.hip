@@ -14,6 +14,7 @@
 //   fmeasure_hist:  per image a (pr_num+1)-bin histogram of bin(p) = #{i : th[i] <= p} over all pixels and over gt != 0;
 //                  suffix sums of it are Eval_Fmeasure's y_temp.sum() and tp for every threshold.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -240,7 +241,7 @@ extern "C" int cavp_seg_confusion_nchw(const float* logits, const void* labels, 
   const bool li = label_dtype == CAVP_I64;
   if (!li && label_dtype != CAVP_F32) return CAVP_ERR_UNSUPPORTED;
   if (((uintptr_t)labels & (li ? 7 : 3)) || ((uintptr_t)M & 7) || ((uintptr_t)logits & 3)) return CAVP_ERR_ALIGN;
-  const bool vec = (HW & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)labels & 15) == 0;
+  const bool vec = (HW & 3) == 0 && al16(logits) && al16(labels);
   const bool lds = (K + 1) * K <= kLdsBins;
   const long long quads = (long long)N * ((HW + 3) >> 2);
   // one quad per thread for B=32 at 224^2 (1568 workgroups, all resident); each workgroup flushes its non-zero LDS bins once
@@ -250,7 +251,7 @@ extern "C" int cavp_seg_confusion_nchw(const float* logits, const void* labels, 
   unsigned long long* m = (unsigned long long*)M;
   if (li) launch_confusion(vec, lds, grid, shm, s, logits, (const long long*)labels, N, C, HW, K, ignore, m);
   else launch_confusion(vec, lds, grid, shm, s, logits, (const float*)labels, N, C, HW, K, ignore, m);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_mask_iou_stats(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t N,
@@ -266,7 +267,7 @@ extern "C" int cavp_mask_iou_stats(const void* pred, int32_t pred_dtype, const v
   else if (pi) mask_iou_stats_kernel<long long, float><<<grid, kThreads, 0, s>>>((const long long*)pred, (const float*)target, HW, o);
   else if (ti) mask_iou_stats_kernel<float, long long><<<grid, kThreads, 0, s>>>((const float*)pred, (const long long*)target, HW, o);
   else mask_iou_stats_kernel<float, float><<<grid, kThreads, 0, s>>>((const float*)pred, (const float*)target, HW, o);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, const void* gt, int32_t gt_dtype, const float* thresholds, int32_t N, int32_t C,
@@ -283,5 +284,5 @@ extern "C" int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, co
   hipStream_t s = (hipStream_t)stream;
   if (gi) fmeasure_hist_kernel<long long><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const long long*)gt, thresholds, C, channel, HW, pr_num, hist);
   else fmeasure_hist_kernel<float><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const float*)gt, thresholds, C, channel, HW, pr_num, hist);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }

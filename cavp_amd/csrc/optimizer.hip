@@ -9,6 +9,7 @@
 //        p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
 // HBM-bound streaming: 3 reads + 2 writes (SGD) / 4 reads + 3 writes (Adam) of 4 bytes per parameter.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -78,5 +79,5 @@ extern "C" int cavp_optimizer_step(const cavp_opt_job* jobs_device, int32_t njob
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   optimizer_step_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(jobs_device, njobs, lr_sgd, lr_adam, momentum, beta1,
                                                                       beta2, eps, (float)bc1, (float)sqrt(bc2), step == 1);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }

@@ -2,6 +2,7 @@
 // LayerNorm, the sigmoid attention gate, BN folding and weight packing.  All NHWC, 16-byte vector accesses along
 // the channel dimension, wave64 shuffles for the row reductions.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -464,17 +465,13 @@ __global__ __launch_bounds__(256) void cast_vec8_kernel(const S* __restrict__ s,
   }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool dtype_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
-#define CHECK_LAUNCH() return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH
-
 }  // namespace
 
 extern "C" int cavp_abi_version(void) { return CAVP_ABI_VERSION; }
 
 CavpDetState g_cavp_det = {nullptr, 0};
 extern "C" int cavp_set_deterministic(void* scratch, size_t bytes) {
-  if (scratch && (((uintptr_t)scratch & 15) || bytes < (1u << 20))) return CAVP_ERR_BAD_ARG;
+  if (scratch && (!al16(scratch) || bytes < (1u << 20))) return CAVP_ERR_BAD_ARG;
   g_cavp_det.scratch = (float*)scratch;
   g_cavp_det.floats = scratch ? bytes / sizeof(float) : 0;
   return CAVP_OK;
@@ -497,7 +494,7 @@ extern "C" int cavp_conv3x3_smallcin_nchw(int32_t dtype, const float* x, const f
                                           const float* shift, void* y, int32_t N, int32_t Cin, int32_t H, int32_t W,
                                           int32_t Cout, int32_t stride, int32_t act, void* stream) {
   if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || stride <= 0) return CAVP_ERR_BAD_ARG;
-  if (!dtype_ok(dtype) || Cin < 1 || Cin > 3 || Cout % 16 || Cout > 128) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype) || Cin < 1 || Cin > 3 || Cout % 16 || Cout > 128) return CAVP_ERR_UNSUPPORTED;
   if (!al16(y)) return CAVP_ERR_ALIGN;
   const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
   const int G = Cout / 16, TW = 2 * (256 / G);
@@ -520,10 +517,8 @@ extern "C" int cavp_conv3x3_smallcin_nchw(int32_t dtype, const float* x, const f
       CHECK_LAUNCH();
     }
   }
-  if (dtype == CAVP_F32)
-    conv3x3_smallcin_kernel<float><<<(int)nb, 256, lds, s>>>(x, w, scale, shift, (float*)y, N, Cin, H, W, Cout, stride, Ho, Wo, act, tiles_w);
-  else
-    conv3x3_smallcin_kernel<bf16_t><<<(int)nb, 256, lds, s>>>(x, w, scale, shift, (bf16_t*)y, N, Cin, H, W, Cout, stride, Ho, Wo, act, tiles_w);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    conv3x3_smallcin_kernel<T><<<(int)nb, 256, lds, s>>>(x, w, scale, shift, (T*)y, N, Cin, H, W, Cout, stride, Ho, Wo, act, tiles_w); });
   CHECK_LAUNCH();
 }
 
@@ -531,8 +526,8 @@ extern "C" int cavp_maxpool_nhwc(int32_t dtype, const void* x, void* y, uint8_t*
                                  int32_t C, int32_t k, int32_t stride, int32_t pad, void* stream) {
   if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0) return CAVP_ERR_BAD_ARG;
   if (argmax && ((uintptr_t)argmax & 7)) return CAVP_ERR_ALIGN;
-  if (!dtype_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  const int VE = dt_ve(dtype);
   if (C % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(y)) return CAVP_ERR_ALIGN;
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
@@ -540,10 +535,8 @@ extern "C" int cavp_maxpool_nhwc(int32_t dtype, const void* x, void* y, uint8_t*
   const long long total = (long long)N * Ho * Wo * (C / VE);
   const int nb = nblocks(total, 256, 16384);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    maxpool_kernel<float><<<nb, 256, 0, s>>>((const float*)x, (float*)y, (unsigned char*)argmax, N, H, W, C, k, stride, pad, Ho, Wo);
-  else
-    maxpool_kernel<bf16_t><<<nb, 256, 0, s>>>((const bf16_t*)x, (bf16_t*)y, (unsigned char*)argmax, N, H, W, C, k, stride, pad, Ho, Wo);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    maxpool_kernel<T><<<nb, 256, 0, s>>>((const T*)x, (T*)y, (unsigned char*)argmax, N, H, W, C, k, stride, pad, Ho, Wo); });
   CHECK_LAUNCH();
 }
 
@@ -552,8 +545,8 @@ extern "C" int cavp_maxpool_affine_nhwc(int32_t dtype, const void* x, const floa
                                         int32_t pad, void* stream) {
   if (!x || !y || !scale || !shift || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0) return CAVP_ERR_BAD_ARG;
   if (argmax && ((uintptr_t)argmax & 7)) return CAVP_ERR_ALIGN;
-  if (!dtype_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  const int VE = dt_ve(dtype);
   if (C % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(y)) return CAVP_ERR_ALIGN;
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
@@ -561,23 +554,19 @@ extern "C" int cavp_maxpool_affine_nhwc(int32_t dtype, const void* x, const floa
   const long long total = (long long)N * Ho * Wo * (C / VE);
   const int nb = nblocks(total, 256, 16384);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    maxpool_kernel<float, true><<<nb, 256, 0, s>>>((const float*)x, (float*)y, (unsigned char*)argmax, N, H, W, C, k, stride, pad, Ho, Wo, scale, shift, act);
-  else
-    maxpool_kernel<bf16_t, true><<<nb, 256, 0, s>>>((const bf16_t*)x, (bf16_t*)y, (unsigned char*)argmax, N, H, W, C, k, stride, pad, Ho, Wo, scale, shift, act);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    maxpool_kernel<T, true><<<nb, 256, 0, s>>>((const T*)x, (T*)y, (unsigned char*)argmax, N, H, W, C, k, stride, pad, Ho, Wo, scale, shift, act); });
   CHECK_LAUNCH();
 }
 
 extern "C" int cavp_global_avgpool_nhwc(int32_t dtype, const void* x, float* y, int32_t N, int32_t HW, int32_t C,
                                         int32_t ldx, void* stream) {
   if (!x || !y || N <= 0 || HW <= 0 || C <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
-  if (!dtype_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((C + 63) / 64, N);
-  if (dtype == CAVP_F32)
-    gap_kernel<float><<<grid, 256, 0, s>>>((const float*)x, y, HW, C, ldx);
-  else
-    gap_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, y, HW, C, ldx);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    gap_kernel<T><<<grid, 256, 0, s>>>((const T*)x, y, HW, C, ldx); });
   CHECK_LAUNCH();
 }
 
@@ -586,17 +575,15 @@ extern "C" int cavp_bilinear_nhwc(int32_t dtype, const void* x, void* y, int32_t
                                   void* stream) {
   if (!x || !y || N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || ldx < C || ldy < C)
     return CAVP_ERR_BAD_ARG;
-  if (!dtype_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE || ldy % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(y)) return CAVP_ERR_ALIGN;
   const long long total = (long long)N * Ho * Wo * (C / VE);
   const int nb = nblocks(total, 256, 16384);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    bilinear_nhwc_kernel<float><<<nb, 256, 0, s>>>((const float*)x, (float*)y, N, Hi, Wi, C, ldx, Ho, Wo, ldy, align_corners);
-  else
-    bilinear_nhwc_kernel<bf16_t><<<nb, 256, 0, s>>>((const bf16_t*)x, (bf16_t*)y, N, Hi, Wi, C, ldx, Ho, Wo, ldy, align_corners);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bilinear_nhwc_kernel<T><<<nb, 256, 0, s>>>((const T*)x, (T*)y, N, Hi, Wi, C, ldx, Ho, Wo, ldy, align_corners); });
   CHECK_LAUNCH();
 }
 
@@ -604,14 +591,12 @@ extern "C" int cavp_bilinear_nhwc_to_nchw(int32_t dtype, const void* x, float* y
                                           int32_t C, int32_t ldx, int32_t Ho, int32_t Wo, int32_t align_corners,
                                           void* stream) {
   if (!x || !y || N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
-  if (!dtype_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
   const long long total = (long long)N * Ho * Wo;
   const int nb = nblocks(total, 256, 16384);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    bilinear_to_nchw_kernel<float><<<nb, 256, 0, s>>>((const float*)x, y, N, Hi, Wi, C, ldx, Ho, Wo, align_corners);
-  else
-    bilinear_to_nchw_kernel<bf16_t><<<nb, 256, 0, s>>>((const bf16_t*)x, y, N, Hi, Wi, C, ldx, Ho, Wo, align_corners);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bilinear_to_nchw_kernel<T><<<nb, 256, 0, s>>>((const T*)x, y, N, Hi, Wi, C, ldx, Ho, Wo, align_corners); });
   CHECK_LAUNCH();
 }
 
@@ -625,20 +610,18 @@ extern "C" int cavp_bn_fold(const float* gamma, const float* beta, const float* 
 extern "C" int cavp_pack_weight_ohwi(int32_t dtype, const float* w, void* o, int32_t Cout, int32_t Cin, int32_t KH,
                                      int32_t KW, void* stream) {
   if (!w || !o || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return CAVP_ERR_BAD_ARG;
-  if (!dtype_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
   const long long total = (long long)Cout * Cin * KH * KW;
   const int nb = nblocks(total, 256, 8192);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    pack_ohwi_kernel<float><<<nb, 256, 0, s>>>(w, (float*)o, Cout, Cin, KH * KW);
-  else
-    pack_ohwi_kernel<bf16_t><<<nb, 256, 0, s>>>(w, (bf16_t*)o, Cout, Cin, KH * KW);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    pack_ohwi_kernel<T><<<nb, 256, 0, s>>>(w, (T*)o, Cout, Cin, KH * KW); });
   CHECK_LAUNCH();
 }
 
 extern "C" int cavp_cast(int32_t sdt, const void* src, int32_t ddt, void* dst, int64_t n, void* stream) {
   if (!src || !dst || n <= 0) return CAVP_ERR_BAD_ARG;
-  if (!dtype_ok(sdt) || !dtype_ok(ddt)) return CAVP_ERR_UNSUPPORTED;
+  if (!dt_ok(sdt) || !dt_ok(ddt)) return CAVP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (n % 8 == 0 && al16(src) && al16(dst)) {
     const long long n8 = n / 8;
@@ -692,7 +675,7 @@ extern "C" int cavp_zero_bytes(void* p, size_t nbytes, void* stream) {
   long long nb = ((long long)(nbytes / 16) + 255) / 256;
   nb = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
   zero_bytes_kernel<<<dim3((unsigned)nb), 256, 0, (hipStream_t)stream>>>((unsigned*)p, (long long)(nbytes / 4));
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }
 
 // *table[i] += inc for n int64 counters scattered in device memory (nn.BatchNorm2d.num_batches_tracked of every layer: one launch)
@@ -704,14 +687,14 @@ static __global__ __launch_bounds__(256) void i64_add_table_kernel(const long lo
 extern "C" int cavp_i64_add_table(const int64_t* table_dev, int32_t n, int64_t inc, void* stream) {
   if (!table_dev || n <= 0) return CAVP_ERR_BAD_ARG;
   i64_add_table_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, (hipStream_t)stream>>>((const long long*)table_dev, n, (long long)inc);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }
 
 extern "C" int cavp_zero_ranges_f32(float* base, const int64_t* table_dev, int32_t nranges, int64_t max_len, void* stream) {
   if (!base || !table_dev || nranges <= 0 || max_len <= 0) return CAVP_ERR_BAD_ARG;
-  if ((uintptr_t)base & 15) return CAVP_ERR_ALIGN;
+  if (!al16(base)) return CAVP_ERR_ALIGN;
   long long nb = (max_len / 4 + 255) / 256;
   nb = nb < 1 ? 1 : (nb > 512 ? 512 : nb);
   zero_ranges_kernel<<<dim3((unsigned)nb, (unsigned)nranges), 256, 0, (hipStream_t)stream>>>(base, (const long long*)table_dev);
-  return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
+  CHECK_LAUNCH();
 }

@@ -1,6 +1,7 @@
 // PVTv2 (models/visual/backbones/pvt/pvt.py) specific kernels for gfx950: MFMA spatial-reduction attention with a
 // wavefront softmax, depth-wise 3x3 conv (+bias +GELU) and the 7x7/stride-4 overlapping patch embedding.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -385,15 +386,13 @@ __global__ __launch_bounds__(256) void conv_smallcin_kxk_kernel(const float* __r
   }
 }
 
-inline bool dt_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
 }  // namespace
-#define CHECK_LAUNCH() return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH
 
 extern "C" int cavp_sra_attention(int32_t dtype, const void* q, const void* kv, void* o, int32_t B, int32_t Nq, int32_t Nk,
                                   int32_t heads, int32_t head_dim, float scale, void* stream) {
   if (!q || !kv || !o || B <= 0 || Nq <= 0 || Nk <= 0 || heads <= 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || head_dim != 64 || Nk > 256) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)q & 15) || ((uintptr_t)kv & 15) || ((uintptr_t)o & 15)) return CAVP_ERR_ALIGN;
+  if (!al16(q) || !al16(kv) || !al16(o)) return CAVP_ERR_ALIGN;
   const int es = dtype == CAVP_F32 ? 4 : 2;
   const int lds = 2 * 256 * 64 * es;
   hipStream_t s = (hipStream_t)stream;
@@ -405,10 +404,8 @@ extern "C" int cavp_sra_attention(int32_t dtype, const void* q, const void* kv, 
   }
   const int qpw = cavp_sra_blocks_per_wg(Nq, B * heads);
   dim3 grid(((Nq + 63) / 64 + qpw - 1) / qpw, B * heads);
-  if (dtype == CAVP_F32)
-    sra_attention_kernel<float><<<grid, 256, lds, s>>>((const float*)q, (const float*)kv, (float*)o, Nq, Nk, heads, scale, qpw);
-  else
-    sra_attention_kernel<bf16_t><<<grid, 256, lds, s>>>((const bf16_t*)q, (const bf16_t*)kv, (bf16_t*)o, Nq, Nk, heads, scale, qpw);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    sra_attention_kernel<T><<<grid, 256, lds, s>>>((const T*)q, (const T*)kv, (T*)o, Nq, Nk, heads, scale, qpw); });
   CHECK_LAUNCH();
 }
 
@@ -422,28 +419,24 @@ int dwconv_launch(int32_t dtype, const void* x, const float* w9c, const float* b
                   int32_t W, int32_t C, int32_t act, int flip, void* stream) {
   if (!x || !w9c || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
   if (aux && act != CAVP_ACT_GELU) return CAVP_ERR_BAD_ARG;   // the second output is gelu'(t)
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)aux) & 15) return CAVP_ERR_ALIGN;
+  if (!al16(x) || !al16(y) || !al16(aux)) return CAVP_ERR_ALIGN;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE) return CAVP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int SW = 32 / VE;
   const long long strips_total = (long long)N * H * ((W + SW - 1) / SW) * (C / VE);
-  if (W >= SW && strips_total < 0x7fffffffll && (((uintptr_t)w9c | (uintptr_t)bias) & 15) == 0 && C % 4 == 0) {
+  if (W >= SW && strips_total < 0x7fffffffll && al16(w9c) && al16(bias) && C % 4 == 0) {
     long long nb = (strips_total + 255) / 256;
     if (nb > 32768) nb = 32768;
-    if (dtype == CAVP_F32)
-      dwconv3x3_strip_kernel<float><<<(int)nb, 256, 0, s>>>((const float*)x, w9c, bias, (float*)y, N, H, W, C, act, (float*)aux, flip);
-    else
-      dwconv3x3_strip_kernel<bf16_t><<<(int)nb, 256, 0, s>>>((const bf16_t*)x, w9c, bias, (bf16_t*)y, N, H, W, C, act, (bf16_t*)aux, flip);
+    cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+      dwconv3x3_strip_kernel<T><<<(int)nb, 256, 0, s>>>((const T*)x, w9c, bias, (T*)y, N, H, W, C, act, (T*)aux, flip); });
     CHECK_LAUNCH();
   }
   long long nb = ((long long)N * H * W * (C / VE) + 255) / 256;
   if (nb > 32768) nb = 32768;
-  if (dtype == CAVP_F32)
-    dwconv3x3_kernel<float><<<(int)nb, 256, 0, s>>>((const float*)x, w9c, bias, (float*)y, N, H, W, C, act, (float*)aux, flip);
-  else
-    dwconv3x3_kernel<bf16_t><<<(int)nb, 256, 0, s>>>((const bf16_t*)x, w9c, bias, (bf16_t*)y, N, H, W, C, act, (bf16_t*)aux, flip);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    dwconv3x3_kernel<T><<<(int)nb, 256, 0, s>>>((const T*)x, w9c, bias, (T*)y, N, H, W, C, act, (T*)aux, flip); });
   CHECK_LAUNCH();
 }
 }  // namespace
@@ -476,9 +469,7 @@ extern "C" int cavp_conv_smallcin_kxk_nchw(int32_t dtype, const float* x_nchw, c
   if (nb > 8192) nb = 8192;
   const size_t lds = (size_t)Cin * KS * KS * Cout * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    conv_smallcin_kxk_kernel<float><<<(int)nb, 256, lds, s>>>(x_nchw, w_oihw, bias, (float*)y_nhwc, N, Cin, H, W, Cout, KS, stride, pad, Ho, Wo);
-  else
-    conv_smallcin_kxk_kernel<bf16_t><<<(int)nb, 256, lds, s>>>(x_nchw, w_oihw, bias, (bf16_t*)y_nhwc, N, Cin, H, W, Cout, KS, stride, pad, Ho, Wo);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    conv_smallcin_kxk_kernel<T><<<(int)nb, 256, lds, s>>>(x_nchw, w_oihw, bias, (T*)y_nhwc, N, Cin, H, W, Cout, KS, stride, pad, Ho, Wo); });
   CHECK_LAUNCH();
 }

@@ -4,6 +4,7 @@
 // stochastic-depth residual add.  The attention backward exists twice: on the f32 matrix pipe (v_mfma_f32_16x16x4f32, the
 // f32 parity path) and on v_mfma_f32_16x16x32_bf16 for bf16 storage.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -694,9 +695,7 @@ __global__ __launch_bounds__(256) void sra_bwd_kv_reduce_kernel(const float* __r
   }
 }
 
-inline bool dt_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
 }  // namespace
-#define CHECK_LAUNCH() return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH
 
 // row statistics (log-sum-exp, delta) + the dK / dV slabs of the query splits: splits * B * Nk * 2C floats with
 // splits <= 256 / (B * heads) and Nk <= 256, i.e. at most 256 * 256 * 128 floats whatever the shape
@@ -717,9 +716,7 @@ extern "C" int cavp_sra_attention_bwd_to(int32_t dtype, const void* q, const voi
   if (!q || !kv || !dout || !dq || !dkv || !workspace || B <= 0 || Nq <= 0 || Nk <= 0 || heads <= 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || !dt_ok(dkv_dtype) || head_dim != 64 || Nk > 256) return CAVP_ERR_UNSUPPORTED;
   if (workspace_bytes < cavp_sra_attention_bwd_workspace_bytes(B, Nq, heads)) return CAVP_ERR_WORKSPACE;
-  if (((uintptr_t)q & 15) || ((uintptr_t)kv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dq & 15) || ((uintptr_t)dkv & 15) ||
-      ((uintptr_t)workspace & 15))
-    return CAVP_ERR_ALIGN;
+  if (!al16(q) || !al16(kv) || !al16(dout) || !al16(dq) || !al16(dkv) || !al16(workspace)) return CAVP_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   static bool attr = false;
   if (!attr) {
@@ -755,13 +752,13 @@ extern "C" int cavp_sra_attention_bwd_to(int32_t dtype, const void* q, const voi
     sra_bwd_kv_bf16_kernel<<<gb, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)kv, (const bf16_t*)dout, stats, kv_out, Nq, Nk, heads,
                                               scale, slab);
   }
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   if (via_slabs) {
     const long long n4 = (long long)(slab / 4);
     long long nb = (n4 + 255) / 256;
     if (nb > 2048) nb = 2048;
-    if (dkv_dtype == CAVP_F32) sra_bwd_kv_reduce_kernel<float><<<(int)nb, 256, 0, s>>>(slabs, (float*)dkv, n4, splits, slab);
-    else sra_bwd_kv_reduce_kernel<bf16_t><<<(int)nb, 256, 0, s>>>(slabs, (bf16_t*)dkv, n4, splits, slab);
+    cavp_dispatch_dtype(dkv_dtype, [&](auto t) { using T = decltype(t);
+      sra_bwd_kv_reduce_kernel<T><<<(int)nb, 256, 0, s>>>(slabs, (T*)dkv, n4, splits, slab); });
   }
   CHECK_LAUNCH();
 }
@@ -775,7 +772,7 @@ extern "C" int cavp_dwconv3x3_bwd(int32_t dtype, const void* x, const void* dy, 
                                   float* dbias, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !dy || !dw_c133 || N <= 0 || H <= 0 || W <= 0 || C <= 0 || ((w9c == nullptr) != (dx == nullptr))) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || C % 8) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)w9c) & 15) return CAVP_ERR_ALIGN;
+  if (!al16(x) || !al16(dy) || !al16(dx) || !al16(w9c)) return CAVP_ERR_ALIGN;
   const long long total = (long long)N * H * W;
   const int gx = (C / 4 + 15) / 16;
   long long ppb = 256;
@@ -797,10 +794,10 @@ extern "C" int cavp_dwconv3x3_bwd(int32_t dtype, const void* x, const void* dy, 
   hipStream_t s = (hipStream_t)stream;
 #define DW_LAUNCH(T, DX) dwconv3x3_wgrad_kernel<T, DX><<<grid, 256, 0, s>>>((const T*)x, (const T*)dy, dw_c133, dbias, N, H, W, C, \
                                                                             (int)ppb, part_dw, part_db, w9c, (T*)dx)
-  if (dtype == CAVP_F32) { if (dx) DW_LAUNCH(float, true); else DW_LAUNCH(float, false); }
-  else { if (dx) DW_LAUNCH(bf16_t, true); else DW_LAUNCH(bf16_t, false); }
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    if (dx) DW_LAUNCH(T, true); else DW_LAUNCH(T, false); });
 #undef DW_LAUNCH
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   if (part_dw) {
     if (cavp_det_finish(part_dw, nsplit, 9 * C, dw_c133, nullptr, s) != hipSuccess) return CAVP_ERR_LAUNCH;
     if (dbias && cavp_det_finish(part_db, nsplit, C, dbias, nullptr, s) != hipSuccess) return CAVP_ERR_LAUNCH;
@@ -812,49 +809,42 @@ extern "C" int cavp_smallcin_kxk_im2col(int32_t dtype, const float* x_nchw, void
                                         int32_t W, int32_t KS, int32_t stride, int32_t pad, int32_t Kpad, void* stream) {
   if (!x_nchw || !cols || N <= 0 || H <= 0 || W <= 0 || stride <= 0 || KS <= 0 || pad < 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || Cin < 1 || Cin > 3 || Kpad % 8 || Kpad < Cin * KS * KS) return CAVP_ERR_UNSUPPORTED;
-  if ((uintptr_t)cols & 15) return CAVP_ERR_ALIGN;
+  if (!al16(cols)) return CAVP_ERR_ALIGN;
   const int Ho = (H + 2 * pad - KS) / stride + 1, Wo = (W + 2 * pad - KS) / stride + 1;
   const long long total = (long long)N * Ho * Wo * (Kpad / 8);
   long long nb = (total + 255) / 256;
   if (nb > 32768) nb = 32768;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    smallcin_kxk_im2col_kernel<float><<<(int)nb, 256, 0, s>>>(x_nchw, (float*)cols, N, Cin, H, W, KS, stride, pad, Ho, Wo, Kpad);
-  else
-    smallcin_kxk_im2col_kernel<bf16_t><<<(int)nb, 256, 0, s>>>(x_nchw, (bf16_t*)cols, N, Cin, H, W, KS, stride, pad, Ho, Wo, Kpad);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    smallcin_kxk_im2col_kernel<T><<<(int)nb, 256, 0, s>>>(x_nchw, (T*)cols, N, Cin, H, W, KS, stride, pad, Ho, Wo, Kpad); });
   CHECK_LAUNCH();
 }
 
 extern "C" int cavp_space_to_depth(int32_t dtype, const void* src, void* dst, int32_t B, int32_t H, int32_t W, int32_t C,
                                    int32_t s, int32_t inverse, void* stream) {
   if (!src || !dst || B <= 0 || H <= 0 || W <= 0 || C <= 0 || s <= 0) return CAVP_ERR_BAD_ARG;
-  if (!dt_ok(dtype) || H % s || W % s || C % (dtype == CAVP_F32 ? 4 : 8)) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return CAVP_ERR_ALIGN;
-  const long long total = (long long)B * H * W * (C / (dtype == CAVP_F32 ? 4 : 8));
+  if (!dt_ok(dtype) || H % s || W % s || C % dt_ve(dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (!al16(src) || !al16(dst)) return CAVP_ERR_ALIGN;
+  const long long total = (long long)B * H * W * (C / dt_ve(dtype));
   long long nb = (total + 255) / 256;
   if (nb > 16384) nb = 16384;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    space_to_depth_kernel<float><<<(int)nb, 256, 0, st>>>((const float*)src, (float*)dst, B, H, W, C, s, inverse);
-  else
-    space_to_depth_kernel<bf16_t><<<(int)nb, 256, 0, st>>>((const bf16_t*)src, (bf16_t*)dst, B, H, W, C, s, inverse);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    space_to_depth_kernel<T><<<(int)nb, 256, 0, st>>>((const T*)src, (T*)dst, B, H, W, C, s, inverse); });
   CHECK_LAUNCH();
 }
 
 extern "C" int cavp_row_scale_add(int32_t dtype, const void* x, const void* branch, const float* sample_scale, void* out,
                                   int32_t B, int64_t per_sample, void* stream) {
   if (!branch || !sample_scale || !out || B <= 0 || per_sample <= 0) return CAVP_ERR_BAD_ARG;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (!dt_ok(dtype) || per_sample % VE) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)branch & 15) || ((uintptr_t)out & 15) || ((uintptr_t)x & 15)) return CAVP_ERR_ALIGN;
+  if (!al16(branch) || !al16(out) || !al16(x)) return CAVP_ERR_ALIGN;
   const long long psv = per_sample / VE, total = psv * B;
   long long nb = (total + 255) / 256;
   if (nb > 16384) nb = 16384;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    row_scale_add_kernel<float><<<(int)nb, 256, 0, st>>>((const float*)x, (const float*)branch, sample_scale, (float*)out, psv, total);
-  else
-    row_scale_add_kernel<bf16_t><<<(int)nb, 256, 0, st>>>((const bf16_t*)x, (const bf16_t*)branch, sample_scale, (bf16_t*)out, psv,
-                                                          total);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    row_scale_add_kernel<T><<<(int)nb, 256, 0, st>>>((const T*)x, (const T*)branch, sample_scale, (T*)out, psv, total); });
   CHECK_LAUNCH();
 }

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -21,9 +22,6 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {  // d act
 }
 
 inline int cdiv_h(long long a, long long b) { return (int)((a + b - 1) / b); }
-inline bool dt_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-#define CHECK_LAUNCH() return hipGetLastError() == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH
 
 // ------------------------------------------------------------------------------------------------------------
 // Column reductions over [rows][C] (C contiguous).  256 threads = 16 column groups (VE channels each) x 16 row
@@ -232,7 +230,7 @@ inline int flat_rows_per_block(long long rows, int C, int es, int CV, long long 
 
 template <int MODE>
 int launch_col_reduce(int dtype, ColArgs& a, hipStream_t s) {
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   // (measured: the contiguous geometry helps the read + write kernels, 1.69 -> 1.23 ms per step for scale_shift_act,
   // but not the reductions - 1.59 -> 1.85 ms for the BN backward reduce - so it stays behind CAVP_FLAT_REDUCE=1)
   static const bool flat_reduce = cavp_knob_str("CAVP_FLAT_REDUCE") != nullptr;
@@ -241,10 +239,8 @@ int launch_col_reduce(int dtype, ColArgs& a, hipStream_t s) {
     const int CV = a.C / VE;
     a.rows_per_block = flat_rows_per_block(a.rows, a.C, 16 / VE, CV, 32 << 10, 4096);   // <= 4096 atomics per channel
     const int gx = (int)((a.rows + a.rows_per_block - 1) / a.rows_per_block);
-    if (dtype == CAVP_F32)
-      col_reduce_flat_kernel<float, MODE><<<gx, 256, 0, s>>>(a, CV);
-    else
-      col_reduce_flat_kernel<bf16_t, MODE><<<gx, 256, 0, s>>>(a, CV);
+    cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+      col_reduce_flat_kernel<T, MODE><<<gx, 256, 0, s>>>(a, CV); });
     CHECK_LAUNCH();
   }
   const int CG = a.C <= 8 * VE ? 8 : 16;   // column groups per workgroup
@@ -265,15 +261,11 @@ int launch_col_reduce(int dtype, ColArgs& a, hipStream_t s) {
   bool det_err;
   a.part = cavp_det_scratch(gx, a.C, &det_err);
   if (det_err) return CAVP_ERR_WORKSPACE;
-  if (dtype == CAVP_F32) {
-    if (CG == 8) col_reduce_kernel<float, MODE, 8><<<dim3(gx, gy), 256, 0, s>>>(a);
-    else col_reduce_kernel<float, MODE, 16><<<dim3(gx, gy), 256, 0, s>>>(a);
-  } else {
-    if (CG == 8) col_reduce_kernel<bf16_t, MODE, 8><<<dim3(gx, gy), 256, 0, s>>>(a);
-    else col_reduce_kernel<bf16_t, MODE, 16><<<dim3(gx, gy), 256, 0, s>>>(a);
-  }
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    if (CG == 8) col_reduce_kernel<T, MODE, 8><<<dim3(gx, gy), 256, 0, s>>>(a);
+    else col_reduce_kernel<T, MODE, 16><<<dim3(gx, gy), 256, 0, s>>>(a); });
   if (a.part) {
-    if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
     return cavp_det_finish(a.part, gx, a.C, a.out0, MODE == 2 ? nullptr : a.out1, s) == hipSuccess ? CAVP_OK : CAVP_ERR_LAUNCH;
   }
   CHECK_LAUNCH();
@@ -1628,11 +1620,9 @@ extern "C" int cavp_pack_weights_multi(int32_t dtype, const cavp_pack_job* jobs,
       blk += (long long)d.tiles_ci * ((jb.Cout + kPackTCO - 1) / kPackTCO);
       if (blk > 0x7fffffffll) return CAVP_ERR_UNSUPPORTED;
     }
-    if (dtype == CAVP_F32)
-      pack_multi_kernel<float><<<(int)blk, 256, 0, s>>>(a);
-    else
-      pack_multi_kernel<bf16_t><<<(int)blk, 256, 0, s>>>(a);
-    if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+    cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+      pack_multi_kernel<T><<<(int)blk, 256, 0, s>>>(a); });
+    if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   }
   return CAVP_OK;
 }
@@ -1647,7 +1637,7 @@ extern "C" int cavp_colstats(int32_t dtype, const void* x, const float* shift, i
                              float* sum, float* sumsq, void* stream) {
   if (!x || !sum || !sumsq || rows <= 0 || C <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || rows > 0x7fffffff) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x)) return CAVP_ERR_ALIGN;
   ColArgs a{};
@@ -1707,7 +1697,7 @@ extern "C" int cavp_scale_shift_act(int32_t dtype, const void* x, const float* s
                                     int32_t ldy, int32_t act, void* stream) {
   if (!x || !y || rows <= 0 || C <= 0 || ldx < C || ldy < C || (residual && ldr < C)) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE || ldy % VE || (residual && ldr % VE)) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || !al16(y) || (residual && !al16(residual))) return CAVP_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
@@ -1725,18 +1715,14 @@ extern "C" int cavp_scale_shift_act(int32_t dtype, const void* x, const float* s
     static const int flat_kb = cavp_knob_int("CAVP_FLAT_SSA_KB", 16);
     const int rpb = flat_rows_per_block(rows, C, 16 / VE, CV, (long long)flat_kb << 10, 1 << 20);
     const int gx = (int)((rows + rpb - 1) / rpb);
-    if (dtype == CAVP_F32)
-      scale_shift_act_flat_kernel<float><<<gx, 256, 0, s>>>((const float*)x, scale, shift, (const float*)residual, (float*)y, rows, rpb, CV, ldx, ldr, ldy, act);
-    else
-      scale_shift_act_flat_kernel<bf16_t><<<gx, 256, 0, s>>>((const bf16_t*)x, scale, shift, (const bf16_t*)residual, (bf16_t*)y, rows, rpb, CV, ldx, ldr, ldy, act);
+    cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+      scale_shift_act_flat_kernel<T><<<gx, 256, 0, s>>>((const T*)x, scale, shift, (const T*)residual, (T*)y, rows, rpb, CV, ldx, ldr, ldy, act); });
     CHECK_LAUNCH();
   }
   dim3 grid;
   const RowLoop g = row_loop_geometry(rows, C, VE, grid);
-  if (dtype == CAVP_F32)
-    scale_shift_act_kernel<float><<<grid, 256, 0, s>>>((const float*)x, scale, shift, (const float*)residual, (float*)y, g, ldx, ldr, ldy, act);
-  else
-    scale_shift_act_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, scale, shift, (const bf16_t*)residual, (bf16_t*)y, g, ldx, ldr, ldy, act);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    scale_shift_act_kernel<T><<<grid, 256, 0, s>>>((const T*)x, scale, shift, (const T*)residual, (T*)y, g, ldx, ldr, ldy, act); });
   CHECK_LAUNCH();
 }
 
@@ -1787,7 +1773,7 @@ extern "C" int cavp_bn_act_bwd_reduce(int32_t dtype, const void* dy, const void*
   if (!dy || !z || !mean || !rstd || !sum_g || !sum_gz || rows <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
   if (!y && act != CAVP_ACT_NONE && (!fwd_scale || !fwd_shift)) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || rows > 0x7fffffff) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ld_dy % VE || (y && ld_y % VE) || ld_z % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(dy) || (y && !al16(y)) || !al16(z)) return CAVP_ERR_ALIGN;
   ColArgs a{};
@@ -1820,7 +1806,7 @@ extern "C" int cavp_bn_act_bwd_apply_acc(int32_t dtype, const void* dy, const vo
     return CAVP_ERR_BAD_ARG;
   if (!y && act != CAVP_ACT_NONE && (!fwd_scale || !fwd_shift)) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ld_dy % VE || (y && ld_y % VE) || ld_z % VE || ld_dz % VE || (g_out && ld_g % VE)) return CAVP_ERR_UNSUPPORTED;
   if (!al16(dy) || (y && !al16(y)) || !al16(z) || !al16(dz) || (g_out && !al16(g_out))) return CAVP_ERR_ALIGN;
   const float inv_m = (float)(1.0 / (double)rows);
@@ -1830,18 +1816,14 @@ extern "C" int cavp_bn_act_bwd_apply_acc(int32_t dtype, const void* dy, const vo
     static const int flat_kb = cavp_knob_int("CAVP_FLAT_APPLY_KB", 16);
     const int rpb = flat_rows_per_block(rows, C, 16 / VE, CV, (long long)flat_kb << 10, 1 << 20);
     const int gx = (int)((rows + rpb - 1) / rpb);
-    if (dtype == CAVP_F32)
-      bn_bwd_apply_flat_kernel<float><<<gx, 256, 0, s>>>((const float*)dy, (const float*)y, (const float*)z, mean, rstd, gamma, sum_g, sum_gz, inv_m, (float*)dz, (float*)g_out, rows, rpb, CV, ld_dy, ld_y, ld_z, ld_dz, ld_g, act, fwd_scale, fwd_shift, dbeta_acc, dgamma_acc);
-    else
-      bn_bwd_apply_flat_kernel<bf16_t><<<gx, 256, 0, s>>>((const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)z, mean, rstd, gamma, sum_g, sum_gz, inv_m, (bf16_t*)dz, (bf16_t*)g_out, rows, rpb, CV, ld_dy, ld_y, ld_z, ld_dz, ld_g, act, fwd_scale, fwd_shift, dbeta_acc, dgamma_acc);
+    cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+      bn_bwd_apply_flat_kernel<T><<<gx, 256, 0, s>>>((const T*)dy, (const T*)y, (const T*)z, mean, rstd, gamma, sum_g, sum_gz, inv_m, (T*)dz, (T*)g_out, rows, rpb, CV, ld_dy, ld_y, ld_z, ld_dz, ld_g, act, fwd_scale, fwd_shift, dbeta_acc, dgamma_acc); });
     CHECK_LAUNCH();
   }
   dim3 grid;
   const RowLoop g = row_loop_geometry(rows, C, VE, grid);
-  if (dtype == CAVP_F32)
-    bn_bwd_apply_kernel<float><<<grid, 256, 0, s>>>((const float*)dy, (const float*)y, (const float*)z, mean, rstd, gamma, sum_g, sum_gz, inv_m, (float*)dz, (float*)g_out, g, ld_dy, ld_y, ld_z, ld_dz, ld_g, act, fwd_scale, fwd_shift, dbeta_acc, dgamma_acc);
-  else
-    bn_bwd_apply_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)z, mean, rstd, gamma, sum_g, sum_gz, inv_m, (bf16_t*)dz, (bf16_t*)g_out, g, ld_dy, ld_y, ld_z, ld_dz, ld_g, act, fwd_scale, fwd_shift, dbeta_acc, dgamma_acc);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bn_bwd_apply_kernel<T><<<grid, 256, 0, s>>>((const T*)dy, (const T*)y, (const T*)z, mean, rstd, gamma, sum_g, sum_gz, inv_m, (T*)dz, (T*)g_out, g, ld_dy, ld_y, ld_z, ld_dz, ld_g, act, fwd_scale, fwd_shift, dbeta_acc, dgamma_acc); });
   CHECK_LAUNCH();
 }
 
@@ -1849,32 +1831,28 @@ extern "C" int cavp_act_bwd(int32_t dtype, const void* dy, const void* ref, void
                             int32_t ld_dy, int32_t ld_ref, int32_t ld_dx, int32_t act, void* stream) {
   if (!dy || !ref || !dx || rows <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ld_dy % VE || ld_ref % VE || ld_dx % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(dy) || !al16(ref) || !al16(dx)) return CAVP_ERR_ALIGN;
   long long nb = (rows * (C / VE) + 255) / 256;
   if (nb > 16384) nb = 16384;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    act_bwd_kernel<float><<<(int)nb, 256, 0, s>>>((const float*)dy, (const float*)ref, (float*)dx, rows, C, ld_dy, ld_ref, ld_dx, act);
-  else
-    act_bwd_kernel<bf16_t><<<(int)nb, 256, 0, s>>>((const bf16_t*)dy, (const bf16_t*)ref, (bf16_t*)dx, rows, C, ld_dy, ld_ref, ld_dx, act);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    act_bwd_kernel<T><<<(int)nb, 256, 0, s>>>((const T*)dy, (const T*)ref, (T*)dx, rows, C, ld_dy, ld_ref, ld_dx, act); });
   CHECK_LAUNCH();
 }
 
 extern "C" int cavp_add(int32_t dtype, const void* a, const void* b, void* out, int64_t n, void* stream) {
   if (!a || !b || !out || n <= 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (n % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(a) || !al16(b) || !al16(out)) return CAVP_ERR_ALIGN;
   long long nb = (n / VE + 255) / 256;
   if (nb > 16384) nb = 16384;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    add_kernel<float><<<(int)nb, 256, 0, s>>>((const float*)a, (const float*)b, (float*)out, n);
-  else
-    add_kernel<bf16_t><<<(int)nb, 256, 0, s>>>((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    add_kernel<T><<<(int)nb, 256, 0, s>>>((const T*)a, (const T*)b, (T*)out, n); });
   CHECK_LAUNCH();
 }
 
@@ -1882,7 +1860,7 @@ extern "C" int cavp_colsum(int32_t dtype, const void* x, int64_t rows, int32_t C
                            void* stream) {
   if (!x || !out || rows <= 0 || C <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || rows > 0x7fffffff) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x)) return CAVP_ERR_ALIGN;
   ColArgs a{};
@@ -1959,14 +1937,12 @@ extern "C" int cavp_col_tile_stats(int32_t dtype, const void* x, int64_t rows, i
                                    void* stream) {
   if (!x || !tile_stats || rows <= 0 || C <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype) || rows > 0x7fffffff) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x) || ((uintptr_t)tile_stats & 7)) return CAVP_ERR_ALIGN;
   const dim3 grid((unsigned)((rows + 127) / 128), cdiv_h(C, 16 * VE));
-  if (dtype == CAVP_F32)
-    col_tile_stats_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)x, tile_stats, rows, C, ldx);
-  else
-    col_tile_stats_kernel<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x, tile_stats, rows, C, ldx);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    col_tile_stats_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T*)x, tile_stats, rows, C, ldx); });
   CHECK_LAUNCH();
 }
 
@@ -2007,14 +1983,12 @@ extern "C" int cavp_colsum_groups(int32_t dtype, const void* x, int32_t groups, 
                                   float* out, void* stream) {
   if (!x || !out || groups <= 0 || rows_per_group <= 0 || C <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ldx % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x)) return CAVP_ERR_ALIGN;
   const dim3 grid(groups, cdiv_h(C, 16 * VE));
-  if (dtype == CAVP_F32)
-    colsum_groups_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)x, out, rows_per_group, C, ldx);
-  else
-    colsum_groups_kernel<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x, out, rows_per_group, C, ldx);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    colsum_groups_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T*)x, out, rows_per_group, C, ldx); });
   CHECK_LAUNCH();
 }
 
@@ -2023,7 +1997,7 @@ extern "C" int cavp_maxpool_bwd_nhwc(int32_t dtype, const uint8_t* argmax, const
   const void* x = argmax;
   if (!x || !dy || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE) return CAVP_ERR_UNSUPPORTED;
   if (((uintptr_t)x & 7) || !al16(dy) || !al16(dx)) return CAVP_ERR_ALIGN;
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
@@ -2035,16 +2009,12 @@ extern "C" int cavp_maxpool_bwd_nhwc(int32_t dtype, const uint8_t* argmax, const
     int sh = -1;
     if ((CV & (CV - 1)) == 0) { sh = 0; while ((1 << sh) < CV) ++sh; }
     const dim3 grid((W * CV + 255) / 256, N * H);
-    if (dtype == CAVP_F32)
-      maxpool_bwd_s2_rows_kernel<float><<<grid, 256, 0, s>>>(argmax, (const float*)dy, (float*)dx, H, W, C, k, pad, Ho, Wo, sh);
-    else
-      maxpool_bwd_s2_rows_kernel<bf16_t><<<grid, 256, 0, s>>>(argmax, (const bf16_t*)dy, (bf16_t*)dx, H, W, C, k, pad, Ho, Wo, sh);
+    cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+      maxpool_bwd_s2_rows_kernel<T><<<grid, 256, 0, s>>>(argmax, (const T*)dy, (T*)dx, H, W, C, k, pad, Ho, Wo, sh); });
     CHECK_LAUNCH();
   }
-  if (dtype == CAVP_F32)
-    maxpool_bwd_kernel<float><<<(int)nb, 256, 0, s>>>(argmax, (const float*)dy, (float*)dx, N, H, W, C, k, stride, pad, Ho, Wo);
-  else
-    maxpool_bwd_kernel<bf16_t><<<(int)nb, 256, 0, s>>>(argmax, (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C, k, stride, pad, Ho, Wo);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    maxpool_bwd_kernel<T><<<(int)nb, 256, 0, s>>>(argmax, (const T*)dy, (T*)dx, N, H, W, C, k, stride, pad, Ho, Wo); });
   CHECK_LAUNCH();
 }
 
@@ -2054,16 +2024,14 @@ extern "C" int cavp_bilinear_bwd_nhwc(int32_t dtype, const void* dy, void* dx, i
   if (!dy || !dx || N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || ld_dx < C || ld_dy < C)
     return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ld_dx % VE || ld_dy % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(dy) || !al16(dx)) return CAVP_ERR_ALIGN;
   long long nb = ((long long)N * Hi * Wi * (C / VE) + 255) / 256;
   if (nb > 32768) nb = 32768;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    bilinear_bwd_nhwc_kernel<float><<<(int)nb, 256, 0, s>>>((const float*)dy, (float*)dx, N, Hi, Wi, C, ld_dx, Ho, Wo, ld_dy, align_corners);
-  else
-    bilinear_bwd_nhwc_kernel<bf16_t><<<(int)nb, 256, 0, s>>>((const bf16_t*)dy, (bf16_t*)dx, N, Hi, Wi, C, ld_dx, Ho, Wo, ld_dy, align_corners);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bilinear_bwd_nhwc_kernel<T><<<(int)nb, 256, 0, s>>>((const T*)dy, (T*)dx, N, Hi, Wi, C, ld_dx, Ho, Wo, ld_dy, align_corners); });
   CHECK_LAUNCH();
 }
 
@@ -2077,10 +2045,8 @@ extern "C" int cavp_bilinear_bwd_nchw_to_nhwc(int32_t dtype, const float* dy_nch
   long long nb = ((long long)N * Hi * Wi * C + 255) / 256;
   if (nb > 32768) nb = 32768;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    bilinear_bwd_from_nchw_kernel<float><<<(int)nb, 256, 0, s>>>(dy_nchw, (float*)dx, N, n_valid, Hi, Wi, C, ld_dx, Ho, Wo, align_corners);
-  else
-    bilinear_bwd_from_nchw_kernel<bf16_t><<<(int)nb, 256, 0, s>>>(dy_nchw, (bf16_t*)dx, N, n_valid, Hi, Wi, C, ld_dx, Ho, Wo, align_corners);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bilinear_bwd_from_nchw_kernel<T><<<(int)nb, 256, 0, s>>>(dy_nchw, (T*)dx, N, n_valid, Hi, Wi, C, ld_dx, Ho, Wo, align_corners); });
   CHECK_LAUNCH();
 }
 
@@ -2088,16 +2054,14 @@ extern "C" int cavp_bcast_add_nhwc(int32_t dtype, void* x, const float* v, float
                                    int32_t C, int32_t ld, void* stream) {
   if (!x || !v || N <= 0 || HW <= 0 || C <= 0 || ld < C) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
-  const int VE = dtype == CAVP_F32 ? 4 : 8;
+  const int VE = dt_ve(dtype);
   if (C % VE || ld % VE) return CAVP_ERR_UNSUPPORTED;
   if (!al16(x)) return CAVP_ERR_ALIGN;
   long long nb = ((long long)N * HW * (C / VE) + 255) / 256;
   if (nb > 16384) nb = 16384;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    bcast_add_kernel<float><<<(int)nb, 256, 0, s>>>((float*)x, v, alpha, N, HW, C, ld);
-  else
-    bcast_add_kernel<bf16_t><<<(int)nb, 256, 0, s>>>((bf16_t*)x, v, alpha, N, HW, C, ld);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bcast_add_kernel<T><<<(int)nb, 256, 0, s>>>((T*)x, v, alpha, N, HW, C, ld); });
   CHECK_LAUNCH();
 }
 
@@ -2182,12 +2146,9 @@ extern "C" int cavp_upsample_ce_head(int32_t dtype, const void* lo, const int64_
   hipStream_t s = (hipStream_t)stream;
   const long long* lab = (const long long*)labels;
   int st;
-  if (dtype == CAVP_F32)
-    st = head_launch<float>((const float*)lo, lab, n_img, n_total, C, Hi, Wi, ld, Ho, Wo, align_corners, ignore_index,
-                            grad_scale, loss, (float*)dlo, lse, scratch2, s);
-  else
-    st = head_launch<bf16_t>((const bf16_t*)lo, lab, n_img, n_total, C, Hi, Wi, ld, Ho, Wo, align_corners,
-                             ignore_index, grad_scale, loss, (bf16_t*)dlo, lse, scratch2, s);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    st = head_launch<T>((const T*)lo, lab, n_img, n_total, C, Hi, Wi, ld, Ho, Wo, align_corners, ignore_index,
+                        grad_scale, loss, (T*)dlo, lse, scratch2, s); });
   if (st != CAVP_OK) return st;
   CHECK_LAUNCH();
 }
@@ -2243,18 +2204,16 @@ extern "C" int cavp_conv3x3_smallcin_wgrad(int32_t dtype, const float* x_nchw, c
         smallcin_wgrad_mfma_kernel<2><<<grid, 256, lds, s>>>(x_nchw, (const bf16_t*)dy_nhwc, part, N, Cin, H, W, pl.Ho, pl.Wo, tw, (int)items);
       else
         smallcin_wgrad_mfma_kernel<1><<<grid, 256, lds, s>>>(x_nchw, (const bf16_t*)dy_nhwc, part, N, Cin, H, W, pl.Ho, pl.Wo, tw, (int)items);
-      if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+      if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
       smallcin_wgrad_sum_kernel<<<128, 256, 0, s>>>(part, grid, dw_oihw, Cin * 9);
       CHECK_LAUNCH();
     }
   }
   long long nb = (pl.M + 255) / 256;
   if (nb > 16384) nb = 16384;
-  if (dtype == CAVP_F32)
-    smallcin_im2col_kernel<float, 28><<<(int)nb, 256, 0, s>>>(x_nchw, (float*)col, N, Cin, H, W, stride, pl.Ho, pl.Wo);
-  else
-    smallcin_im2col_kernel<bf16_t, 32><<<(int)nb, 256, 0, s>>>(x_nchw, (bf16_t*)col, N, Cin, H, W, stride, pl.Ho, pl.Wo);
-  if (hipGetLastError() != hipSuccess) return CAVP_ERR_LAUNCH;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);   // KP = pl.KP: 28 (f32) / 32 (bf16)
+    smallcin_im2col_kernel<T, sizeof(T) == 4 ? 28 : 32><<<(int)nb, 256, 0, s>>>(x_nchw, (T*)col, N, Cin, H, W, stride, pl.Ho, pl.Wo); });
+  if (launch_status() != CAVP_OK) return CAVP_ERR_LAUNCH;
   if (cavp_zero_f32_async(tmp, (size_t)Cout * pl.KP * 4, s) != hipSuccess) return CAVP_ERR_LAUNCH;
   const int st = cavp_conv2d_wgrad_nhwc(&pl.d, col, dy_nhwc, tmp, nullptr, ws, pl.ws_bytes, stream);
   if (st != CAVP_OK) return st;
@@ -2279,9 +2238,7 @@ extern "C" int cavp_pack_weight_dgrad(int32_t dtype, const float* w_oihw, void* 
   long long nb = ((long long)Cout * Cin * KH * KW + 255) / 256;
   if (nb > 8192) nb = 8192;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CAVP_F32)
-    pack_dgrad_kernel<float><<<(int)nb, 256, 0, s>>>(w_oihw, (float*)w_t, Cout, Cin, KH, KW);
-  else
-    pack_dgrad_kernel<bf16_t><<<(int)nb, 256, 0, s>>>(w_oihw, (bf16_t*)w_t, Cout, Cin, KH, KW);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    pack_dgrad_kernel<T><<<(int)nb, 256, 0, s>>>(w_oihw, (T*)w_t, Cout, Cin, KH, KW); });
   CHECK_LAUNCH();
 }

@@ -123,23 +123,9 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, dw_ohwi: torch.Tensor, *, kh
     """dw_ohwi (f32 [Cout][kh][kw][Cin]) += wgrad(x, dy); dbias (optional f32 [Cout]) += column sums of dy.
     dw_oihw=True: the destination is a torch-layout [Cout][Cin][kh][kw] gradient (no separate unpack pass).
     overwrite=True: dw = wgrad(x, dy) (beta = 0: the destination is neither read nor assumed to be zero)."""
-    _need_gpu(x, dy, dw_ohwi, dbias)
-    n, h, w, cin, ldx = _nhwc(x)
-    n2, ho, wo, cout, ldy = _nhwc(dy)
-    if n2 != n or x.dtype != dy.dtype or dw_ohwi.dtype != torch.float32 or dw_ohwi.numel() != cout * kh * kw * cin \
-            or not dw_ohwi.is_contiguous():
-        raise _lib.CavpError("conv2d_wgrad: shape / dtype mismatch")
-    eho = (h + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    ewo = (w + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-    if (ho, wo) != (eho, ewo):
-        raise _lib.CavpError("conv2d_wgrad: dy extent does not match the forward conv")
-    d = ConvDesc(dtype=dtype_code(x.dtype), N=n, H=h, W=w, Cin=cin, ldx=ldx, Cout=cout, ldy=ldy, KH=kh, KW=kw,
-                 stride=stride, pad=pad, dil=dil, ldr=0, act=0, splitk=splitk, tile=0, up=0, Ho=0, Wo=0, stride_w=0,
-                 dw_oihw=int(dw_oihw), dw_overwrite=int(overwrite))
+    d = _wgrad_desc(x, dy, dw_ohwi, kh, kw, stride, pad, dil, splitk, dbias, dw_oihw, overwrite)
     lib = _lib.load()
     ws = ops.workspace(lib.cavp_conv2d_wgrad_workspace_bytes(C.byref(d)), x.device)
-    if dbias is not None and (dbias.dtype != torch.float32 or dbias.numel() != cout or not dbias.is_contiguous()):
-        raise _lib.CavpError("conv2d_wgrad: dbias must be a dense f32 [Cout] tensor")
     _check(lib.cavp_conv2d_wgrad_nhwc(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw_ohwi), _ptr(dbias), _ptr(ws),
                                       C.c_size_t(ws.numel() if ws is not None else 0), _s()), "cavp_conv2d_wgrad_nhwc")
     return dw_ohwi

@@ -160,6 +160,17 @@ def test_conv3x3_smallcin(cin, stride, hw, dtype):
     _check(out.permute(0, 3, 1, 2), ref, dtype, "smallcin")
 
 
+def test_conv3x3_smallcin_bf16_narrow_cout():
+    """bf16 with Cout != 64 stays on the generic kernel (the matrix-core version is the 64-channel stems only): 3 x 5 pixels, 16 channels"""
+    ops = _ops()
+    x, wt = _rand(1, 3, 3, 5, seed=18), _rand(16, 3, 3, 3, seed=19, scale=0.3)
+    sc, sh = torch.rand(16, generator=torch.Generator().manual_seed(20)) + 0.5, _rand(16, seed=21)
+    ref = F.relu(F.conv2d(x, wt, None, 1, 1) * sc[None, :, None, None] + sh[None, :, None, None])
+    out = torch.empty((1, 3, 5, 16), dtype=torch.bfloat16, device=DEV)
+    ops.conv3x3_smallcin_nchw(x.to(DEV), wt.to(DEV), out, stride=1, scale=sc.to(DEV), shift=sh.to(DEV), act=ops.ACT_RELU)
+    _check(out.permute(0, 3, 1, 2), ref, torch.bfloat16, "smallcin bf16 cout 16")
+
+
 @pytest.mark.parametrize("cin,stride,hw", [(3, 2, (224, 224)), (1, 1, (96, 64)), (3, 2, (31, 45)), (2, 1, (5, 131))])
 def test_conv3x3_smallcin_bf16_matrix_core_path_keeps_f32_inputs(cin, stride, hw):
     """The bf16 stem conv (Cout = 64) runs on the MFMA with the f32 image and weights split into bf16 hi + lo pairs (round 6): every output

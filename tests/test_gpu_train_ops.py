@@ -419,6 +419,21 @@ def test_bcast_add_and_smallcin_wgrad(dt):
         _check(dw - 0.5, w.grad, dt, f"smallcin wgrad {cin} s{stride} {hw}", 1e-4, 1e-2)
 
 
+def test_smallcin_wgrad_bf16_narrow_cout():
+    """bf16 with Cout != 64 takes the im2col + GEMM route (the fused matrix-core kernel is the 64-channel stems only): 3 x 5 pixels,
+    one 16-byte vector of output channels; the image is bf16-representable, so the route's rounding of the columns is exact."""
+    ops, T = _mods()
+    dt = torch.bfloat16
+    xi = _q(_rand(1, 3, 3, 5, seed=34), dt)
+    w = _rand(8, 3, 3, 3, seed=35, scale=0.3).requires_grad_(True)
+    y = F.conv2d(xi, w, None, 1, 1)
+    dy = _q(_rand(*y.shape, seed=36), dt)
+    y.backward(dy)
+    dw = torch.full((8, 3, 3, 3), 0.5, device=DEV)
+    T.smallcin_wgrad(xi.to(DEV), _nhwc(dy, dt), dw, 1)
+    _check(dw - 0.5, w.grad, dt, "smallcin wgrad bf16 cout 8", 1e-4, 1e-2)
+
+
 @pytest.mark.parametrize("dt", DTYPES, ids=IDS)
 @pytest.mark.parametrize("shape", [(4, 56, 56, 64, 64, 3), (2, 28, 28, 128, 512, 1), (3, 13, 11, 64, 48, 1)])
 def test_fused_bn_statistics_from_conv_epilogue(shape, dt):
