@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(HERE, "libcavp_hip.so")
 
 F32, BF16, I64 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_GELU = 0, 1, 2, 3
-ABI_VERSION = 14
+ABI_VERSION = 15
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH = -1, -2, -3, -4, -5   # cavp_status_t
 WGRAD_GROUP_MAX = 16   # CAVP_WGRAD_GROUP_MAX
 
@@ -157,6 +157,9 @@ PROTOTYPES = {
     "cavp_seg_confusion_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp]),
     "cavp_mask_iou_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp]),
     "cavp_fmeasure_hist": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp]),
+    # ---- mask / probability / confusion counts from the low-resolution logits (ABI 15) ----
+    "cavp_seg_predict_nhwc": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i64,
+                                     _vp, _vp]),
 }
 
 _lib = None

@@ -574,10 +574,14 @@ class CAVP(nn.Module):
             fea_v_proj = fea_v_proj.repeat(B // Bv, 1, 1)
         return fus.view(B, h, w, Cc), fea_v_proj.view(B, h, w, Cc), attn
 
-    def _cls_hip(self, fusion, P, input_shape):
+    def _cls_lowres_hip(self, fusion, P):
+        """Decoder head up to the classifier conv: low-resolution logits NHWC [B, h, w, C]."""
         x = self._conv(fusion, P["head0"], act=ACT_RELU)
         x = self._conv(x, P["head1"], act=ACT_RELU)
-        lo = self._conv(x, P["cls"])
+        return self._conv(x, P["cls"])
+
+    def _cls_hip(self, fusion, P, input_shape):
+        lo = self._cls_lowres_hip(fusion, P)
         out = torch.empty((fusion.shape[0], P["cls"].cout) + tuple(input_shape), dtype=torch.float32, device=fusion.device)
         return ops.bilinear_to_nchw(lo, out, align_corners=False), lo
 
@@ -588,6 +592,18 @@ class CAVP(nn.Module):
         return ops.cast(t.contiguous(), torch.empty(t.shape, dtype=torch.float32, device=t.device))
 
     def _forward_hip(self, image, audio, duplicate_visual: bool, taps: Optional[dict] = None, shuffle=None):
+        fusion, fea_v_proj, attn, fea_a, lo, input_shape = self._lowres_hip(image, audio, duplicate_visual, taps, shuffle)
+        out = torch.empty((fusion.shape[0], lo.shape[-1]) + input_shape, dtype=torch.float32, device=fusion.device)
+        out_pred = ops.bilinear_to_nchw(lo, out, align_corners=False)
+        out_fusion = self._as_f32(fusion).permute(0, 3, 1, 2)
+        pack = {"audio": self._as_f32(fea_a)[:, :, None, None],
+                "visual": self._as_f32(fea_v_proj).permute(0, 3, 1, 2),
+                "attn_v": attn.unsqueeze(-1)}
+        return out_pred, out_fusion, pack
+
+    def _lowres_hip(self, image, audio, duplicate_visual: bool, taps: Optional[dict] = None, shuffle=None):
+        """The forward up to the classifier conv: (fusion, fea_v_proj, attn, fea_a, low-resolution logits NHWC [B, h, w, C],
+        input_shape).  _forward_hip upsamples the logits; predict / predict_lowres hand them to ops.seg_predict instead."""
         if not image.is_cuda:
             raise CavpError("CAVP (MI355X path) needs inputs on a HIP device: there is no CPU fallback")
         if image.dtype != torch.float32 or audio.dtype != torch.float32:
@@ -630,17 +646,13 @@ class CAVP(nn.Module):
             raise CavpError(f"audio batch {fea_a.shape[0]} vs visual batch {fea_v.shape[0]}: train mode expects audio of 2B "
                             f"(cavp_model.py:181), inference one clip per image")
         fusion, fea_v_proj, attn = self._fusion_hip(fea_v, fea_a, P)
-        out_pred, lo = self._cls_hip(fusion, P, input_shape)
+        lo = self._cls_lowres_hip(fusion, P)
         if taps is not None:
             for i, f in enumerate(feats):
                 taps[f"layer{i + 1}"] = f.permute(0, 3, 1, 2)
             taps.update(aspp=aspp.permute(0, 3, 1, 2), fea_v=fea_v.permute(0, 3, 1, 2), fea_a=fea_a,
                         logits_lowres=lo.permute(0, 3, 1, 2))
-        out_fusion = self._as_f32(fusion).permute(0, 3, 1, 2)
-        pack = {"audio": self._as_f32(fea_a)[:, :, None, None],
-                "visual": self._as_f32(fea_v_proj).permute(0, 3, 1, 2),
-                "attn_v": attn.unsqueeze(-1)}
-        return out_pred, out_fusion, pack
+        return fusion, fea_v_proj, attn, fea_a, lo, input_shape
 
     # -- reference API ------------------------------------------------------------------------------------------
     def _stage_on_tape(self, mods, *inputs) -> bool:
@@ -726,6 +738,35 @@ class CAVP(nn.Module):
 
     def forward_inference(self, image, audio=None):
         return self._forward_hip(image, audio, duplicate_visual=False)
+
+    def _predict_checks(self, what, image, audio):
+        if not isinstance(image, torch.Tensor) or not isinstance(audio, torch.Tensor) or not image.is_cuda or not audio.is_cuda:
+            raise CavpError(f"CAVP.{what} (MI355X path) needs image and audio on a HIP device: there is no CPU fallback")
+        if any(m.training for m in self.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)):
+            raise CavpError(f"CAVP.{what} runs the eval kernels (folded BatchNorm) but a BatchNorm layer is in training mode: "
+                            f"call model.eval() first")
+
+    def predict_lowres(self, image, audio):
+        """The eval forward up to the classifier conv: low-resolution logits as the NHWC view [B, h, w, C] in the compute dtype
+        (h, w = the backbone's 1/4-resolution grid).  Feed them to MIoU / ForegroundDetect.update_lowres or ops.seg_predict: the
+        full-resolution [B, C, H, W] logits are never allocated.  Runs under no_grad; the model must be in eval mode."""
+        self._predict_checks("predict_lowres", image, audio)
+        with torch.no_grad():
+            return self._lowres_hip(image, audio, duplicate_visual=False)[4]
+
+    def predict(self, image, audio, *, return_prob: bool = False, channel: int = 1):
+        """Class mask of the eval forward: uint8 [B, H, W] = argmax over the classes of the logits `forward(..., eval_mode=True)`
+        returns, exactly, computed from the low-resolution logits in one kernel (ops.seg_predict) without allocating the
+        [B, C, H, W] tensor.  return_prob=True: (mask, prob) with prob f32 [B, H, W] = softmax(logits, 1)[:, channel], the map
+        Eval_Fmeasure takes.  Needs num_classes <= 256."""
+        self._predict_checks("predict", image, audio)
+        with torch.no_grad():
+            lo = self._lowres_hip(image, audio, duplicate_visual=False)[4]
+            shape = (lo.shape[0],) + tuple(image.shape[-2:])
+            mask = torch.empty(shape, dtype=torch.uint8, device=lo.device)
+            prob = torch.empty(shape, dtype=torch.float32, device=lo.device) if return_prob else None
+            ops.seg_predict(lo, shape[1:], mask=mask, prob=prob, channel=channel, align_corners=False)
+        return (mask, prob) if return_prob else mask
 
     def forward_train(self, image, audio=None, shuffle_info=None, ow_flag=False, audio_func=False):
         """cavp_model.py:175-188.  audio_func=False (every reference trainer): `audio` holds 2B clips (matched | shuffled).

@@ -326,6 +326,34 @@ __device__ __forceinline__ void split_index(long long idx, int CV, int W, int H,
   split_pixel(pix, W, H, w, h, n);
 }
 
+// Bilinear resize taps (PyTorch area_pixel_compute_source_index semantics, f32 index math) and the four-tap blend.  One
+// definition for every kernel that must produce the same f32 bits per interpolated value (bilinear_to_nchw_kernel and
+// seg_predict_kernel: the mask is the argmax of exactly what the upsample kernel would have written).
+__device__ __forceinline__ void src_index(int dst, int in, int out, int align, int& i0, int& i1, float& lam) {
+  float src;
+  if (align) {
+    const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+    src = sc * (float)dst;
+  } else {
+    const float sc = (float)in / (float)out;
+    src = sc * ((float)dst + 0.5f) - 0.5f;
+    if (src < 0.f) src = 0.f;
+  }
+  i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  lam = src - (float)i0;
+}
+__device__ __forceinline__ void bilinear_weights(float lh, float lw, float& w00, float& w01, float& w10, float& w11) {
+  w00 = (1.f - lh) * (1.f - lw);
+  w01 = (1.f - lh) * lw;
+  w10 = lh * (1.f - lw);
+  w11 = lh * lw;
+}
+__device__ __forceinline__ float bilinear_blend(float w00, float w01, float w10, float w11, float a, float b, float c, float d) {
+  return w00 * a + w01 * b + w10 * c + w11 * d;
+}
+
 // Bijective XCD-aware block remap (8 XCDs, block b is dispatched to XCD b % 8): gives each XCD a contiguous
 // range of logical tile ids so neighbouring tiles (which share an operand panel) hit the same private L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {

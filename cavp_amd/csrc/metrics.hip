@@ -10,6 +10,8 @@
 //                  non-zero bin; larger K adds straight into M.  The background-correct bin takes most pixels: equal bins are
 //                  merged inside a thread's 4 pixels, and the first bin of the wave is summed across the wave (three ballots)
 //                  before its one atomic.
+//   seg_predict:   the same argmax and counts (and a u8 mask / a softmax-channel probability map) from the model's low-resolution NHWC
+//                  logits: the bilinear upsample is evaluated per pixel in registers, the full-resolution tensor is never written.
 //   mask_iou_stats: per image  sum p*t, sum max(p, t), sum (1-t)(1-p), sum t  in int64.
 //   fmeasure_hist:  per image a (pr_num+1)-bin histogram of bin(p) = #{i : th[i] <= p} over all pixels and over gt != 0;
 //                  suffix sums of it are Eval_Fmeasure's y_temp.sum() and tp for every threshold.
@@ -223,6 +225,198 @@ int chunks_for(long long work, long long per_block, int cap) {
   return (int)(c < 1 ? 1 : (c > cap ? cap : c));
 }
 
+// ---- seg_predict: mask / probability / confusion counts straight from the low-resolution NHWC logits ----------------------------
+// The full-resolution [N][C][Ho][Wo] tensor of bilinear_to_nchw_kernel is never written: a thread interpolates the C logits of
+// its 4 consecutive output pixels of one row ("quad") with that kernel's taps and blend (common.h: the same f32 bits), keeps the
+// running argmax (argmax_step) and, for `prob`, redoes the channel loop for the max-subtracted softmax of fmeasure_hist_kernel.
+// With the x4 ratio of the model head the 4 pixels read at most 3 source columns of 2 source rows: 6 loads per channel (group)
+// instead of 16; any other geometry takes the per-pixel taps.
+
+// taps of one quad; pixels past the row's end repeat the last valid pixel (in-bounds loads, results dropped)
+struct QuadTaps {
+  size_t r0, r1;       // element offsets of the two source rows inside x
+  int w0[4], w1[4];    // source columns of each pixel
+  float w00[4], w01[4], w10[4], w11[4];
+  bool shared;         // all 8 columns lie in w0[0] .. w0[0] + 2
+};
+
+template <typename T, bool kVec>
+__device__ __forceinline__ void load_group(const T* p, float* v) {
+  if constexpr (kVec) VecT<T>::load(p, v);
+  else v[0] = Elem<T>::ld(p);
+}
+
+__device__ __forceinline__ float pick3(int s, float a, float b, float c) { return s == 0 ? a : (s == 1 ? b : c); }
+
+// f(c, v): v[j] = interpolated logit of channel c at pixel j of the quad, for c = 0 .. C-1 in order
+template <typename T, bool kVec, typename F>
+__device__ __forceinline__ void quad_logits(const T* __restrict__ x, const QuadTaps& q, int C, int ldx, F&& f) {
+  constexpr int VE = kVec ? VecT<T>::VE : 1;
+  for (int c0 = 0; c0 < C; c0 += VE) {
+    float v[4][VE];
+    if (q.shared) {
+      float t[2][3][VE];
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int col = q.w0[0] + s <= q.w1[3] ? q.w0[0] + s : q.w1[3];   // w1[3] is the largest column of the quad
+        load_group<T, kVec>(x + q.r0 + (size_t)col * ldx + c0, t[0][s]);
+        load_group<T, kVec>(x + q.r1 + (size_t)col * ldx + c0, t[1][s]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int s0 = q.w0[j] - q.w0[0], s1 = q.w1[j] - q.w0[0];
+#pragma unroll
+        for (int e = 0; e < VE; ++e)
+          v[j][e] = bilinear_blend(q.w00[j], q.w01[j], q.w10[j], q.w11[j], pick3(s0, t[0][0][e], t[0][1][e], t[0][2][e]),
+                                   pick3(s1, t[0][0][e], t[0][1][e], t[0][2][e]), pick3(s0, t[1][0][e], t[1][1][e], t[1][2][e]),
+                                   pick3(s1, t[1][0][e], t[1][1][e], t[1][2][e]));
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float a[VE], b[VE], c[VE], d[VE];
+        load_group<T, kVec>(x + q.r0 + (size_t)q.w0[j] * ldx + c0, a);
+        load_group<T, kVec>(x + q.r0 + (size_t)q.w1[j] * ldx + c0, b);
+        load_group<T, kVec>(x + q.r1 + (size_t)q.w0[j] * ldx + c0, c);
+        load_group<T, kVec>(x + q.r1 + (size_t)q.w1[j] * ldx + c0, d);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) v[j][e] = bilinear_blend(q.w00[j], q.w01[j], q.w10[j], q.w11[j], a[e], b[e], c[e], d[e]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < VE; ++e) {
+      if (c0 + e < C) {
+        const float ve[4] = {v[0][e], v[1][e], v[2][e], v[3][e]};
+        f(c0 + e, ve);
+      }
+    }
+  }
+}
+
+enum { kOutVecMask = 1, kOutVecProb = 2, kOutVecLabels = 4 };   // which per-pixel arrays take one vector access per quad
+
+// kVec: 16-byte channel-group loads (ldx a multiple of the vector, x 16-byte aligned; the groups may run into the row's padding
+// channels, never past the pitch).  kConf: 0 no counts, 1 counts privatised in LDS, 2 counts added straight into M.
+// One thread = one quad; the grid strides over all N * Ho * ceil(Wo / 4) quads with a block-uniform trip count (add_bins ballots).
+template <typename T, bool kVec, int kConf>
+__global__ __launch_bounds__(kThreads) void seg_predict_kernel(const T* __restrict__ x, int N, int Hi, int Wi, int C, int ldx, int Ho,
+                                                              int Wo, int align, unsigned char* __restrict__ mask,
+                                                              float* __restrict__ prob, int channel, const void* __restrict__ labels,
+                                                              int label_f32, int K, long long ignore,
+                                                              unsigned long long* __restrict__ M, int out_vec) {
+  extern __shared__ unsigned hist[];
+  const int nbins = (K + 1) * K;
+  if (kConf == 1) {
+    for (int i = threadIdx.x; i < nbins; i += kThreads) hist[i] = 0u;
+    __syncthreads();
+  }
+  const int qpr = (Wo + 3) >> 2;
+  const long long total = (long long)N * Ho * qpr;
+  for (long long base = (long long)blockIdx.x * kThreads; base < total; base += (long long)gridDim.x * kThreads) {
+    const long long qi = base + threadIdx.x;
+    int b[4] = {-1, -1, -1, -1};
+    if (qi < total) {
+      int qx, ho, n;
+      split_pixel(qi, qpr, Ho, qx, ho, n);
+      const int wo0 = qx * 4, np = Wo - wo0 < 4 ? Wo - wo0 : 4;
+      QuadTaps q;
+      int h0, h1;
+      float lh;
+      src_index(ho, Hi, Ho, align, h0, h1, lh);
+      q.r0 = ((size_t)n * Hi + h0) * Wi * ldx;
+      q.r1 = ((size_t)n * Hi + h1) * Wi * ldx;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float lw;
+        src_index(wo0 + (j < np ? j : np - 1), Wi, Wo, align, q.w0[j], q.w1[j], lw);
+        bilinear_weights(lh, lw, q.w00[j], q.w01[j], q.w10[j], q.w11[j]);
+      }
+      q.shared = q.w1[3] - q.w0[0] <= 2;   // columns never decrease along a row: w0[0] is the smallest, w1[3] the largest
+      const float ninf = -__builtin_huge_valf();
+      float best[4] = {ninf, ninf, ninf, ninf}, mx[4] = {ninf, ninf, ninf, ninf};
+      int idx[4] = {0, 0, 0, 0};
+      quad_logits<T, kVec>(x, q, C, ldx, [&](int c, const float* v) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          argmax_step(v[j], c, best[j], idx[j]);
+          mx[j] = fmaxf(mx[j], v[j]);
+        }
+      });
+      const long long p0 = ((long long)n * Ho + ho) * Wo + wo0;
+      if (mask) {
+        if (out_vec & kOutVecMask) {
+          *(unsigned*)(mask + p0) = (unsigned)idx[0] | ((unsigned)idx[1] << 8) | ((unsigned)idx[2] << 16) | ((unsigned)idx[3] << 24);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (j < np) mask[p0 + j] = (unsigned char)idx[j];
+          }
+        }
+      }
+      if (prob) {   // softmax over the C interpolated logits, channel `channel`: fmeasure_hist_kernel's arithmetic
+        float s[4] = {0.f, 0.f, 0.f, 0.f}, xc[4] = {0.f, 0.f, 0.f, 0.f};
+        quad_logits<T, kVec>(x, q, C, ldx, [&](int c, const float* v) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            s[j] += expf(v[j] - mx[j]);
+            if (c == channel) xc[j] = v[j];
+          }
+        });
+        float pr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pr[j] = expf(xc[j] - mx[j]) / s[j];
+        if (out_vec & kOutVecProb) {
+          *(float4*)(prob + p0) = make_float4(pr[0], pr[1], pr[2], pr[3]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (j < np) prob[p0 + j] = pr[j];
+          }
+        }
+      }
+      if (kConf) {
+        if (label_f32) {
+          const float* lab = (const float*)labels + p0;
+          float t[4] = {0.f, 0.f, 0.f, 0.f};
+          if (out_vec & kOutVecLabels) {
+            const float4 t4 = *(const float4*)lab;
+            t[0] = t4.x; t[1] = t4.y; t[2] = t4.z; t[3] = t4.w;
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if (j < np) t[j] = lab[j];
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(t[j], idx[j], K, ignore) : -1;
+        } else {
+          const long long* lab = (const long long*)labels + p0;
+          long long t[4] = {0, 0, 0, 0};
+          if (out_vec & kOutVecLabels) {
+            const longlong2 t01 = *(const longlong2*)lab, t23 = *(const longlong2*)(lab + 2);
+            t[0] = t01.x; t[1] = t01.y; t[2] = t23.x; t[3] = t23.y;
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if (j < np) t[j] = lab[j];
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(t[j], idx[j], K, ignore) : -1;
+        }
+      }
+    }
+    if (kConf) add_bins<kConf == 1>(b, hist, M);
+  }
+  if (kConf == 1) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nbins; i += kThreads) {
+      const unsigned v = hist[i];
+      if (v) atomicAdd(M + i, (unsigned long long)v);
+    }
+  }
+}
+
 }  // namespace
 
 template <typename LT>
@@ -251,6 +445,52 @@ extern "C" int cavp_seg_confusion_nchw(const float* logits, const void* labels, 
   unsigned long long* m = (unsigned long long*)M;
   if (li) launch_confusion(vec, lds, grid, shm, s, logits, (const long long*)labels, N, C, HW, K, ignore, m);
   else launch_confusion(vec, lds, grid, shm, s, logits, (const float*)labels, N, C, HW, K, ignore, m);
+  CHECK_LAUNCH();
+}
+
+template <typename T>
+void launch_seg_predict(bool vec, int conf, int grid, size_t shm, hipStream_t s, const T* x, int N, int Hi, int Wi, int C, int ldx, int Ho,
+                        int Wo, int align, unsigned char* mask, float* prob, int channel, const void* labels, int label_f32, int K,
+                        long long ignore, unsigned long long* M, int out_vec) {
+#define CAVP_SEG_PREDICT(V, CF) \
+  seg_predict_kernel<T, V, CF><<<grid, kThreads, shm, s>>>(x, N, Hi, Wi, C, ldx, Ho, Wo, align, mask, prob, channel, labels, label_f32, K, \
+                                                         ignore, M, out_vec)
+  if (vec) {
+    if (conf == 0) CAVP_SEG_PREDICT(true, 0);
+    else if (conf == 1) CAVP_SEG_PREDICT(true, 1);
+    else CAVP_SEG_PREDICT(true, 2);
+  } else {
+    if (conf == 0) CAVP_SEG_PREDICT(false, 0);
+    else if (conf == 1) CAVP_SEG_PREDICT(false, 1);
+    else CAVP_SEG_PREDICT(false, 2);
+  }
+#undef CAVP_SEG_PREDICT
+}
+
+extern "C" int cavp_seg_predict_nhwc(int32_t dtype, const void* x, int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t ldx, int32_t Ho,
+                                     int32_t Wo, int32_t align_corners, uint8_t* mask, float* prob, int32_t channel, const void* labels,
+                                     int32_t label_dtype, int32_t K, int64_t ignore, uint64_t* M, void* stream) {
+  if (!x || N <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || ldx < C) return CAVP_ERR_BAD_ARG;
+  if ((!mask && !prob && !M) || (!labels != !M)) return CAVP_ERR_BAD_ARG;
+  if (prob && (channel < 0 || channel >= C)) return CAVP_ERR_BAD_ARG;
+  if (M && K <= 0) return CAVP_ERR_BAD_ARG;
+  if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (mask && C > 256) return CAVP_ERR_UNSUPPORTED;
+  const bool lf = label_dtype == CAVP_F32;
+  if (M && (K < C || K > CAVP_METRICS_MAX_CLASSES || (!lf && label_dtype != CAVP_I64))) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)x & (dtype == CAVP_F32 ? 3 : 1)) || ((uintptr_t)prob & 3) || ((uintptr_t)labels & (lf ? 3 : 7)) || ((uintptr_t)M & 7))
+    return CAVP_ERR_ALIGN;
+  const bool vec = ldx % dt_ve(dtype) == 0 && al16(x);
+  const int conf = !M ? 0 : ((K + 1) * K <= kLdsBins ? 1 : 2);
+  int out_vec = 0;
+  if ((Wo & 3) == 0) out_vec = (((uintptr_t)mask & 3) ? 0 : kOutVecMask) | (al16(prob) ? kOutVecProb : 0) | (al16(labels) ? kOutVecLabels : 0);
+  const long long quads = (long long)N * Ho * ((Wo + 3) >> 2);
+  const int grid = chunks_for(quads, kThreads, conf == 2 ? 4096 : 2048);
+  const size_t shm = conf == 1 ? (size_t)(K + 1) * K * sizeof(unsigned) : 0;
+  hipStream_t s = (hipStream_t)stream;
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    launch_seg_predict<T>(vec, conf, grid, shm, s, (const T*)x, N, Hi, Wi, C, ldx, Ho, Wo, align_corners, mask, prob, channel, labels, lf, K,
+                          ignore, (unsigned long long*)M, out_vec); });
   CHECK_LAUNCH();
 }
 

@@ -344,24 +344,8 @@ __global__ __launch_bounds__(256) void gap_kernel(const T* __restrict__ x, float
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// bilinear resize (PyTorch area_pixel_compute_source_index semantics, f32 index math)
+// bilinear resize (src_index / bilinear_weights / bilinear_blend: common.h)
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void src_index(int dst, int in, int out, int align, int& i0, int& i1, float& lam) {
-  float src;
-  if (align) {
-    const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-    src = sc * (float)dst;
-  } else {
-    const float sc = (float)in / (float)out;
-    src = sc * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-  }
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  lam = src - (float)i0;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear_nhwc_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int Hi,
                                                             int Wi, int C, int ldx, int Ho, int Wo, int ldy, int align) {
@@ -406,11 +390,12 @@ __global__ __launch_bounds__(256) void bilinear_to_nchw_kernel(const T* __restri
     const T* pb = base + ((size_t)h0 * Wi + w1) * ldx;
     const T* pc = base + ((size_t)h1 * Wi + w0) * ldx;
     const T* pd = base + ((size_t)h1 * Wi + w1) * ldx;
-    const float w00 = (1.f - lh) * (1.f - lw), w01 = (1.f - lh) * lw, w10 = lh * (1.f - lw), w11 = lh * lw;
+    float w00, w01, w10, w11;
+    bilinear_weights(lh, lw, w00, w01, w10, w11);
     float* yp = y + (size_t)n * C * Ho * Wo + (size_t)ho * Wo + wo;
     for (int c = 0; c < C; ++c) {
-      const float v = w00 * Elem<T>::ld(pa + c) + w01 * Elem<T>::ld(pb + c) + w10 * Elem<T>::ld(pc + c) +
-                      w11 * Elem<T>::ld(pd + c);
+      const float v = bilinear_blend(w00, w01, w10, w11, Elem<T>::ld(pa + c), Elem<T>::ld(pb + c), Elem<T>::ld(pc + c),
+                                     Elem<T>::ld(pd + c));
       yp[(size_t)c * Ho * Wo] = v;
     }
   }

@@ -17,7 +17,8 @@ Differences from the reference, on purpose:
   * Eval_Fmeasure treats gt as a binary mask (gt != 0), as the AVS trainers feed it;
   * mask_iou's float inputs must be masks (integer values): each pixel is truncated to an integer before summing;
   * device tensors only: there is no CPU path (CavpError).
-Additions: `update(x, y)` (no host sync; no allocation after the first call, so it can be captured in a hipGraph with the eval
+Additions: `update_lowres(lo, y)` (the same counts from the model's low-resolution logits, CAVP.predict_lowres: the full-resolution
+logits are never written), `update(x, y)` (no host sync; no allocation after the first call, so it can be captured in a hipGraph with the eval
 forward), `reset()`, `counts()` (the device-side (K+1) x K confusion counts) and `fmeasure_curve(...)` (the score curve as a
 device tensor, without `.item()`)."""
 from __future__ import annotations
@@ -85,6 +86,23 @@ class _Confusion:
         if self._M is None or self._M.device != x.device:
             self._M = _zeros(((k + 1) * k,), torch.int64, x.device)
         ops.seg_confusion(x.detach(), y, k, self._kernel_ignore, self._M)
+
+    def update_lowres(self, lo: torch.Tensor, y: torch.Tensor, input_shape=None, align_corners: bool = False) -> None:
+        """update() from the low-resolution logits `lo` (NHWC view [B, h, w, C], f32 or bf16: CAVP.predict_lowres): the counts of
+        update(full_res_logits, y) where full_res_logits is the bilinear upsample of `lo` to `input_shape` (default y.shape[1:]),
+        which is never materialised (ops.seg_predict).  No host sync, no allocation after the first call."""
+        if lo.dim() != 4 or y.dim() != 3 or y.shape[0] != lo.shape[0]:
+            raise CavpError(f"{type(self).__name__}: low-res logits [B, h, w, C] and target [B, H, W] required, got "
+                            f"{tuple(lo.shape)} / {tuple(y.shape)}")
+        shape = tuple(y.shape[1:]) if input_shape is None else tuple(int(v) for v in input_shape)
+        if shape != tuple(y.shape[1:]):
+            raise CavpError(f"{type(self).__name__}: input_shape {shape} differs from the target's {tuple(y.shape[1:])}")
+        ops._need_gpu(lo, y)
+        k = self.num_classes
+        if self._M is None or self._M.device != lo.device:
+            self._M = _zeros(((k + 1) * k,), torch.int64, lo.device)
+        ops.seg_predict(lo.detach(), shape, labels=y, num_classes=k, ignore=self._kernel_ignore, M=self._M,
+                        align_corners=align_corners)
 
     def counts(self) -> torch.Tensor:
         """The (K+1) x K confusion counts (int64, on the device; zeros on the CPU before the first update)."""

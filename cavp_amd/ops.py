@@ -548,3 +548,52 @@ def fmeasure_hist(src: torch.Tensor, gt: torch.Tensor, thresholds: torch.Tensor,
                                         int(channel), h * w, pr, _ptr(hist), C.c_void_p(_stream()))
     _lib.check(st, "cavp_fmeasure_hist")
     return hist
+
+
+def seg_predict(lo: torch.Tensor, out_hw, *, mask: Optional[torch.Tensor] = None, prob: Optional[torch.Tensor] = None,
+                channel: int = 1, labels: Optional[torch.Tensor] = None, num_classes: Optional[int] = None, ignore: int = -1,
+                M: Optional[torch.Tensor] = None, align_corners: bool = False):
+    """Class mask, probability map and confusion counts of the bilinearly upsampled logits, from the low-resolution logits `lo`
+    (NHWC view [N, h, w, C], f32 or bf16) in one launch; the [N, C, H, W] tensor bilinear_to_nchw would write is never made, yet
+    the results are those of its output, bit for bit (include/cavp_hip.h, cavp_seg_predict_nhwc).  Each output is optional, at
+    least one is required:
+      mask   dense uint8 [N, H, W]  <- argmax over C (C <= 256);
+      prob   dense f32 [N, H, W]    <- softmax over C, channel `channel`;
+      M      dense int64 (K+1)*K    += confusion counts against `labels` (dense [N, H, W], int64 or float32 holding integers),
+             K = num_classes >= C, bin rule of seg_confusion.
+    Returns (mask, prob, M)."""
+    _need_gpu(lo, mask, prob, labels, M)
+    n, hi, wi, c, ldx = _nhwc(lo)
+    ho, wo = (int(v) for v in out_hw)
+    if mask is None and prob is None and M is None:
+        raise _lib.CavpError("seg_predict: ask for at least one of mask, prob, M")
+    if ho <= 0 or wo <= 0:
+        raise _lib.CavpError(f"seg_predict: bad output size {(ho, wo)}")
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or tuple(mask.shape) != (n, ho, wo)):
+        raise _lib.CavpError(f"seg_predict: mask must be a dense uint8 {(n, ho, wo)} tensor")
+    if mask is not None and c > 256:
+        raise _lib.CavpError(f"seg_predict: a uint8 mask holds at most 256 classes, the logits have {c}")
+    if prob is not None:
+        if prob.dtype != torch.float32 or not prob.is_contiguous() or tuple(prob.shape) != (n, ho, wo):
+            raise _lib.CavpError(f"seg_predict: prob must be a dense float32 {(n, ho, wo)} tensor")
+        if not 0 <= int(channel) < c:
+            raise _lib.CavpError(f"seg_predict: channel {channel} outside the {c} logit channels")
+    if (labels is None) != (M is None):
+        raise _lib.CavpError("seg_predict: labels and M come together")
+    k, code = 0, F32
+    if M is not None:
+        if num_classes is None:
+            raise _lib.CavpError("seg_predict: num_classes is required with M")
+        k = int(num_classes)
+        if tuple(labels.shape) != (n, ho, wo) or not labels.is_contiguous():
+            raise _lib.CavpError(f"seg_predict: dense labels of shape {(n, ho, wo)} required, got {tuple(labels.shape)}")
+        if k < c:
+            raise _lib.CavpError(f"seg_predict: num_classes {k} < logit channels {c}")
+        if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
+            raise _lib.CavpError("seg_predict: M must be a dense int64 tensor of (K+1)*K counts")
+        code = _metric_code(labels, "seg_predict")
+    st = _lib.load().cavp_seg_predict_nhwc(dtype_code(lo.dtype), _ptr(lo), n, hi, wi, c, ldx, ho, wo, int(align_corners), _ptr(mask),
+                                           _ptr(prob), int(channel), _ptr(labels), code, k, int(ignore), _ptr(M),
+                                           C.c_void_p(_stream()))
+    _lib.check(st, f"cavp_seg_predict_nhwc N{n} {hi}x{wi}->{ho}x{wo} C{c} K{k}")
+    return mask, prob, M

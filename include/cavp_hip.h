@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CAVP_ABI_VERSION 14
+#define CAVP_ABI_VERSION 15
 
 typedef enum { CAVP_F32 = 0, CAVP_BF16 = 1, CAVP_I64 = 2 /* ABI 13: metrics inputs only */ } cavp_dtype_t;
 typedef enum { CAVP_ACT_NONE = 0, CAVP_ACT_RELU = 1, CAVP_ACT_LEAKY = 2, CAVP_ACT_GELU = 3 } cavp_act_t;
@@ -582,6 +582,23 @@ int cavp_mask_iou_stats(const void* pred, int32_t pred_dtype, const void* target
  * hist: u32 [N][2][pr_num + 1]. */
 int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, const void* gt, int32_t gt_dtype, const float* thresholds, int32_t N, int32_t C,
                        int32_t channel, int64_t HW, int32_t pr_num, uint32_t* hist, void* stream);
+
+/* ---- ABI 15: segmentation mask, probability map and confusion counts straight from the low-resolution logits ----
+ * x: NHWC logits [N][Hi][Wi][C] (dtype CAVP_F32 / CAVP_BF16, pixel pitch ldx >= C elements: a channel slice of a padded buffer is
+ * fine).  Every output pixel (n, ho, wo) of the Ho x Wo grid gets its C bilinearly interpolated logits - the same taps, weights
+ * and blend, hence the same f32 bits, as the cavp_bilinear_nhwc_to_nchw output - but that [N][C][Ho][Wo] tensor is never
+ * written.  Outputs, each optional (NULL = skipped), at least one required:
+ *   mask   u8  [N][Ho][Wo]: argmax over C (first maximal index, a NaN counts as the maximum, as torch.max).  Needs C <= 256.
+ *   prob   f32 [N][Ho][Wo]: softmax over the C interpolated logits (max-subtracted), channel `channel` (0 <= channel < C).
+ *   M      (K+1) x K u64 counts, together with `labels` (dense [N][Ho][Wo]; label_dtype CAVP_I64, or CAVP_F32 holding integers):
+ *          M[row][p] += 1 with the bin rule of the NCHW confusion entry point above: p = the argmax, label t counted when t >= 0
+ *          and t != ignore, row = t < K ? t : K; K >= C.  Not cleared here.  `labels` and `M` come together.
+ * Any Hi, Wi -> Ho, Wo; the x4 ratio of the model head is the fast case (4 neighbouring pixels share 3 source columns).  16-byte
+ * channel loads when ldx is a multiple of the 16-byte vector and x is 16-byte aligned, scalar loads otherwise; per-pixel arrays
+ * take vector accesses when Wo % 4 == 0 and their base is aligned (mask 4, prob / labels 16 bytes).  No allocation, no sync. */
+int cavp_seg_predict_nhwc(int32_t dtype, const void* x, int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t ldx, int32_t Ho,
+                          int32_t Wo, int32_t align_corners, uint8_t* mask, float* prob, int32_t channel, const void* labels,
+                          int32_t label_dtype, int32_t K, int64_t ignore, uint64_t* M, void* stream);
 
 #ifdef __cplusplus
 }
