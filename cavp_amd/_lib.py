@@ -138,6 +138,10 @@ PROTOTYPES = {
     "cavp_infonce_rows_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _f32, _vp]),
     "cavp_l2norm_bwd_scatter_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64,
                                            _vp]),
+    # ---- contrastive loss on the training tape's [2B][HW][ld] compute-dtype fusion map ----
+    "cavp_contrast_gather_nhwc": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "cavp_contrast_rows_bwd_add": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
+                                          _vp]),
     # ---- PVTv2 ----
     "cavp_sra_attention": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "cavp_dwconv3x3_nhwc": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -837,8 +837,15 @@ class CAVP(nn.Module):
             late += list(self.segment.aspp.parameters()) + list(self.segment.reduce.parameters())
         return {id(p) for p in late}
 
+    def _fusion_hw(self, image):
+        """Spatial size of the fusion map (the first backbone stage's resolution) for an image batch, known before the forward."""
+        H, W = int(image.shape[-2]), int(image.shape[-1])
+        if self.seg_model == "PVT":
+            return (H - 1) // 4 + 1, (W - 1) // 4 + 1                         # 7 x 7 patch embedding, stride 4, pad 3
+        return ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1             # 3 x 3 stem conv stride 2 pad 1, 3 x 3 max-pool stride 2 pad 1
+
     def train_step(self, image, audio, label, ignore_index: int = 255, loss_scale: float = 1.0, all_reduce: bool = True,
-                   _split_hook=None, want_pred: bool = False):
+                   _split_hook=None, want_pred: bool = False, contrast=None, label_shuffle=None, contrast_weight: float = 1.0):
         """MI355X-native fused training step (no torch.autograd): forward_train (batch-stat BN, audio 2B) -> HIP
         cross-entropy on `out[:B] + out[B:]*0` (trainer_cavp_vpo_mono.py:171,187) -> hand-written backward.  Every
         gradient lands in one flat f32 arena (`p.grad` are views of it).  With a torch.distributed process group the
@@ -847,6 +854,11 @@ class CAVP(nn.Module):
         while the backbone backward still runs, the remainder at the end.
         The segmentation head is one fused op (upsample + CE + backward); `want_pred=True`
         additionally materialises the full-resolution prediction into `self._last_outputs[0]` (otherwise None).
+        contrast: a cavp_amd.contrast.ContrastLoss - the step then optimises the reference trainers' full objective
+        `l_ce + contrast_weight * l_ctr` (trainer_cavp_vpo_mono.py:183-189) with l_ctr = contrast(fusion[:B], label, fusion[B:],
+        label_shuffle): the anchors are gathered straight from the compute-dtype NHWC fusion map and their gradient rows are added
+        into its gradient on the tape (TrainPass.grad_tap) - no autograd, no tensor of the map's size.  `label_shuffle` is then
+        required; `self._last_losses = (l_ce, l_ctr)`, both unweighted 1-element device tensors.
         Returns the (local) loss as a 1-element device tensor."""
         from . import train_ops as T
         from .train import (GradArena, TrainPass, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world,
@@ -859,11 +871,23 @@ class CAVP(nn.Module):
                    and m.weight.numel() >= _GRAD_OVERWRITE_MIN} if _GRAD_OVERWRITE_MIN > 0 else set()
             arena = self._grad_arena = GradArena(list(self.parameters()), image.device, late_ids=self._late_grad_ids(),
                                                  no_zero_ids=big)
+        term = None
+        if contrast is not None:
+            from .contrast import ContrastLoss, NativeContrastTerm
+            if not isinstance(contrast, ContrastLoss):
+                raise CavpError("train_step: contrast must be a cavp_amd.contrast.ContrastLoss")
+            if label_shuffle is None:
+                raise CavpError("train_step: contrast needs label_shuffle (the labels of the shuffled-audio half)")
+            if label.dim() != 3 or label.shape[0] != image.shape[0] or tuple(label.shape[-2:]) != tuple(image.shape[-2:]):
+                raise CavpError(f"train_step: labels {tuple(label.shape)} do not match the images {tuple(image.shape)}")
+            # labels -> fusion resolution, plan (device sampler) or label download (host sampler): before any model kernel is queued
+            term = NativeContrastTerm(contrast, label, label_shuffle, self._fusion_hw(image))
         arena.zero()
         tp = TrainPass(self, self.compute_dtype, arena=arena)
         B, C = image.shape[0], self.num_classes
         with torch.no_grad():
-            lo, fusion, fea_v_proj, fea_a, attn = run_train_forward(self, image.contiguous(), audio.contiguous(), tp)
+            lo, fusion, fea_v_proj, fea_a, attn = run_train_forward(self, image.contiguous(), audio.contiguous(), tp,
+                                                                    fusion_tap=term.add_rows if term is not None else None)
             world = dist_world() if all_reduce else 1
             out_pred = None
             if tuple(label.shape[-2:]) != tuple(image.shape[-2:]):
@@ -879,6 +903,12 @@ class CAVP(nn.Module):
                 g = torch.zeros(lo.t.shape, dtype=lo.t.dtype, device=lo.t.device)
                 T.bilinear_bwd_from_nchw(dl, g[..., :C], n_valid=B, align_corners=False)
             lo.set_g(g)
+            if term is not None:
+                term.draw()   # host sampler: torch.randperm, after the forward's own draws (PVT DropPath) as in the reference's loop
+                l_ce = loss
+                l_ctr = term.run(fusion.t, contrast_weight * loss_scale / world)
+                loss = torch.add(l_ce, l_ctr, alpha=float(contrast_weight))
+                self._last_losses = (l_ce, l_ctr)
             early = []
             if _split_hook is not None:
                 tp.on_early_final = _split_hook
@@ -895,30 +925,37 @@ class CAVP(nn.Module):
         return loss
 
     def capture_train_step(self, image, audio, label, ignore_index: int = 255, loss_scale: float = 1.0,
-                           split: Optional[bool] = None):
+                           split: Optional[bool] = None, contrast=None, label_shuffle=None, contrast_weight: float = 1.0):
         """Capture forward_train + CE + backward (about 1000 kernel launches) into hipGraphs and return
         `replay() -> loss`.  `image`, `audio`, `label` are the static input buffers: copy new batches into them before
         each replay.  Weight packing is part of the graph, so replays always see the current parameters.
         Single process: ONE graph.  Data parallel (or `split=True`): TWO graphs cut where the early gradient range is
         final; replay() = graph 1 -> asynchronous RCCL all-reduce of that range -> graph 2 (rest of the backward, runs
-        concurrently with the collective) -> all-reduce of the late range -> join."""
+        concurrently with the collective) -> all-reduce of the late range -> join.
+        contrast / label_shuffle / contrast_weight as in train_step (`label_shuffle` is a static input buffer too).  The criterion
+        must use the device sampler (ContrastLoss.use_device_sampler): its call counter lives on the device, so every replay draws
+        fresh anchors, and `contrast.manual_seed()` between replays restarts the sequence.  All contrast launches are in graph 1."""
         from .train import _no_gc_during_capture, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world
+        if contrast is not None and getattr(contrast, "_dev", None) is None:
+            raise CavpError("capture_train_step: the contrast term can only be captured with the device sampler "
+                            "(ContrastLoss.use_device_sampler); the host sampler reads the labels and draws on the CPU every step")
+        ctr = dict(contrast=contrast, label_shuffle=label_shuffle, contrast_weight=contrast_weight) if contrast is not None else {}
         world = dist_world()
         if split is None:
             split = collectives_on()
         with torch.no_grad():
-            self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False)   # warm-up: workspace, arena
+            self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)   # warm-up: workspace, arena
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False)
+                self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)
             torch.cuda.current_stream().wait_stream(side)
             if not split:
                 graph = torch.cuda.CUDAGraph()
                 # thread_local: other threads (RCCL's watchdog polls its events) must not invalidate the capture
                 with _no_gc_during_capture(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False)
+                    loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False, **ctr)
                 graphs = (graph,)
             else:
                 g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -933,7 +970,7 @@ class CAVP(nn.Module):
                         g2.capture_begin(pool=g1.pool(), capture_error_mode="thread_local")   # shares (and keeps alive) graph 1's allocations
 
                     loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False,
-                                           _split_hook=cut)
+                                           _split_hook=cut, **ctr)
                     g2.capture_end()
                 torch.cuda.current_stream().wait_stream(cap)
                 graphs = (g1, g2)

@@ -13,6 +13,9 @@ Split of work:
 Opt-in: `ContrastLoss.use_device_sampler(max_classes)` moves the sampling onto the device as well (same selection rule,
 Philox4x32-10 keys instead of torch.randperm; include/cavp_hip.h ABI 14).  That path never touches the host between its
 launches, so `loss = crit(...); loss.backward()` can be captured in a hipGraph.
+
+Inside the native training step (`CAVP.train_step(contrast=crit, ...)`) the same chain runs without autograd on the tape's
+compute-dtype NHWC fusion map: `NativeContrastTerm` at the end of this file (cavp_contrast_gather_nhwc / cavp_contrast_rows_bwd_add).
 """
 from __future__ import annotations
 
@@ -416,3 +419,149 @@ class ContrastLoss(nn.Module):
         if plan is None:
             return torch.tensor([0.0], device=gt_match.device)          # contrastive_aud.py:35-36
         return _InfoNCEFn.apply(embeds_match, embeds_shuffle, plan, float(self.temperature), float(self.eps))
+
+
+# ---- the loss on the training tape's fusion map (CAVP.train_step(contrast=...)) ---------------------------------------------------
+def anchor_rows(idx_b, idx_p, n_match: int, B: int, hw: int) -> np.ndarray:
+    """Row of each anchor in the tape's fusion map viewed as [2B * hw, ld]: image idx_b[i] of the match half for i < n_match, image
+    B + idx_b[i] of the shuffle half after it (the addressing of cavp_contrast_gather_nhwc / cavp_contrast_rows_bwd_add)."""
+    b, p = np.asarray(idx_b, dtype=np.int64), np.asarray(idx_p, dtype=np.int64)
+    if b.shape != p.shape or b.ndim != 1 or not 0 <= n_match <= b.shape[0]:
+        raise _lib.CavpError("anchor_rows: idx_b / idx_p must be 1-d of one length, 0 <= n_match <= their length")
+    if b.size and (b.min() < 0 or b.max() >= B or p.min() < 0 or p.max() >= hw):
+        raise _lib.CavpError("anchor_rows: an anchor lies outside the [B] x [hw] map")
+    half = (np.arange(b.shape[0]) >= n_match).astype(np.int64)
+    return (b + half * B) * hw + p
+
+
+def _nhwc_map_args(x: torch.Tensor, what: str):
+    """(B, hw, ld, C) of a fusion map [2B, h, w, C] (or [2B, hw, C]) whose pixels are ld elements apart; raises on anything else."""
+    if not x.is_cuda:
+        raise _lib.CavpError(f"{what}: needs a HIP device tensor (there is no CPU fallback)")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.CavpError(f"{what}: float32 or bfloat16 map required, got {x.dtype}")
+    if x.dim() not in (3, 4) or x.shape[0] % 2 or x.stride(-1) != 1:
+        raise _lib.CavpError(f"{what}: [2B, h, w, C] map with unit channel stride required, got shape {tuple(x.shape)}")
+    n2, Cc, ld = x.shape[0], x.shape[-1], x.stride(-2)
+    hw = x.numel() // (n2 * Cc)
+    dense = x.stride(0) == hw * ld and (x.dim() == 3 or x.shape[2] == 1 or x.stride(1) == x.shape[2] * ld)
+    if not dense or ld < Cc:
+        raise _lib.CavpError(f"{what}: pixels must lie ld elements apart throughout, got strides {x.stride()}")
+    if Cc % 8:
+        raise _lib.CavpError(f"{what}: channel width {Cc} is not a multiple of 8")
+    return n2 // 2, hw, ld, Cc
+
+
+def _plan_args(plan, idx):
+    """(header, idx_b, idx_p, cap, N, n_match) of a DevicePlan, or of a SamplePlan whose index arrays `idx` are on the device."""
+    if isinstance(plan, DevicePlan):
+        return _ptr(plan.header), _ptr(plan.idx_b), _ptr(plan.idx_p), plan.cap, 0, 0
+    return None, _ptr(idx[0]), _ptr(idx[1]), 0, plan.n, plan.n_match
+
+
+def contrast_gather_nhwc(x: torch.Tensor, plan, idx, A: torch.Tensor, norms: torch.Tensor, eps: float = 1e-12) -> None:
+    """A[i] = x_row / max(||x_row||, eps) (f32 [rows, C]) and norms[i] for the plan's anchors, read from the map in its own dtype."""
+    B, hw, ld, Cc = _nhwc_map_args(x, "contrast_gather_nhwc")
+    if A.dtype != torch.float32 or norms.dtype != torch.float32 or not A.is_contiguous() or A.shape[1] != Cc or norms.numel() < A.shape[0]:
+        raise _lib.CavpError("contrast_gather_nhwc: A must be dense f32 [rows, C] with one norm per row")
+    header, ib, ip, cap, n, nm = _plan_args(plan, idx)
+    _lib.check(_lib.load().cavp_contrast_gather_nhwc(ops.dtype_code(x.dtype), _ptr(x), B, hw, ld, Cc, header, ib, ip, cap, n, nm,
+                                                     A.shape[0], C.c_float(eps), _ptr(A), _ptr(norms), C.c_void_p(_stream())),
+               "cavp_contrast_gather_nhwc")
+
+
+def contrast_rows_bwd_add(g: torch.Tensor, plan, idx, dA: torch.Tensor, A: torch.Tensor, norms: torch.Tensor, scale: float = 1.0) -> None:
+    """g_row += scale * (dA_i - A_i <A_i, dA_i>) / norms[i] for the plan's anchors, in place in the map's own dtype."""
+    B, hw, ld, Cc = _nhwc_map_args(g, "contrast_rows_bwd_add")
+    for t in (dA, A):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != Cc:
+            raise _lib.CavpError("contrast_rows_bwd_add: A / dA must be dense f32 [rows, C]")
+    header, ib, ip, cap, n, nm = _plan_args(plan, idx)
+    if min(A.shape[0], dA.shape[0], norms.numel()) < (cap if header is not None else n):
+        raise _lib.CavpError("contrast_rows_bwd_add: A / dA / norms hold fewer rows than the plan")
+    _lib.check(_lib.load().cavp_contrast_rows_bwd_add(ops.dtype_code(g.dtype), _ptr(g), B, hw, ld, Cc, header, ib, ip, cap, n, nm,
+                                                      _ptr(dA), _ptr(A), _ptr(norms), C.c_float(scale), C.c_void_p(_stream())),
+               "cavp_contrast_rows_bwd_add")
+
+
+class NativeContrastTerm:
+    """The contrast term of one native training step (CAVP.train_step(contrast=crit)), without autograd and without a tensor of the
+    fusion map's size: labels -> plan -> gather from the compute-dtype NHWC map -> S -> InfoNCE -> dA, and `add_rows`, the gradient
+    tap that adds the anchors' rows into the map's gradient.  Three calls, in the order the step makes them:
+      __init__   both label maps reduced to `size` on the device; device sampler: the plan (three launches); host sampler: the
+                 download of the reduced labels - before any model kernel is queued, so it waits behind nothing;
+      draw()     host sampler: the torch.randperm draws, in the reference's order (after the forward, whose DropPath may draw too);
+      run()      the chain up to dA on the finished map; returns the unweighted loss, f32 [1] on the device."""
+
+    def __init__(self, crit: "ContrastLoss", label: torch.Tensor, label_shuffle: torch.Tensor, size: Tuple[int, int]):
+        for g in (label, label_shuffle):
+            if not g.is_cuda or g.dim() != 3 or g.is_floating_point() or g.dtype == torch.bool:
+                raise _lib.CavpError("train_step(contrast=...): integer [B, H, W] label maps on the device required")
+        if label.shape != label_shuffle.shape:
+            raise _lib.CavpError(f"train_step(contrast=...): label {tuple(label.shape)} and label_shuffle "
+                                 f"{tuple(label_shuffle.shape)} differ in shape")
+        self.crit, self.size, self.plan, self.saved = crit, tuple(size), None, None
+        self._host = None
+        if crit._dev is not None:
+            max_classes, state = crit._dev
+            if state.device != label.device:
+                raise _lib.CavpError(f"device sampler lives on {state.device}, labels on {label.device}")
+            if label.shape[0] * size[0] * size[1] >= 2 ** 31:
+                raise _lib.CavpError("the device sampler needs B*h*w < 2**31")
+            self.plan = sample_anchors_device(_label_nearest_device(label, self.size), _label_nearest_device(label_shuffle, self.size),
+                                              crit.ignore_idx, crit.max_views, max_classes, state)
+            crit._last_plan = self.plan
+        else:
+            self._host = (downsample_labels(label, self.size), downsample_labels(label_shuffle, self.size))
+
+    def draw(self) -> None:
+        if self._host is not None:
+            self.plan = sample_anchors(self._host[0], self._host[1], self.crit.ignore_idx, self.crit.max_views)   # None: no class qualifies
+
+    def run(self, fusion: torch.Tensor, grad_scale: float) -> torch.Tensor:
+        """fusion: the tape's map [2B, h, w, C].  grad_scale: d(total loss) / d(this term).  Leaves what add_rows needs."""
+        lib, dev, st = _lib.load(), fusion.device, C.c_void_p(_stream())
+        if tuple(fusion.shape[1:3]) != self.size:
+            raise _lib.CavpError(f"train_step(contrast=...): the fusion map is {tuple(fusion.shape[1:3])}, the labels were reduced to {self.size}")
+        plan = self.plan
+        if plan is None:
+            return T.zeros((1,), torch.float32, dev)
+        Cc = fusion.shape[-1]
+        idx = lab = None
+        if isinstance(plan, DevicePlan):
+            npad = (plan.cap + 3) // 4 * 4
+        else:
+            npad = (plan.n + 3) // 4 * 4
+            ib, ip, lab = _upload_i32((plan.b, plan.p, plan.labels), dev)
+            idx = (ib, ip)
+        A = torch.empty((npad, Cc), dtype=torch.float32, device=dev)
+        norms = torch.empty(npad, dtype=torch.float32, device=dev)
+        contrast_gather_nhwc(fusion, plan, idx, A, norms)
+        S = torch.empty((npad, npad), dtype=torch.float32, device=dev)
+        inv_t = torch.full((npad,), 1.0 / self.crit.temperature, dtype=torch.float32, device=dev)
+        ops.linear(A, A.view(npad, 1, 1, Cc), S, scale=inv_t)
+        rows = torch.empty(npad, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dS = torch.empty_like(S)
+        eps = C.c_float(float(self.crit.eps))
+        if isinstance(plan, DevicePlan):
+            _lib.check(lib.cavp_infonce_rows_dev(_ptr(S), _ptr(plan.labels), _ptr(plan.header), plan.cap, npad, eps, _ptr(rows),
+                                                 _ptr(loss), _ptr(dS), C.c_float(1.0), st), "cavp_infonce_rows_dev")
+        else:
+            _lib.check(lib.cavp_infonce_rows(_ptr(S), _ptr(lab), plan.n, npad, eps, _ptr(rows), _ptr(loss), _ptr(dS), C.c_float(1.0), st),
+                       "cavp_infonce_rows")
+        G = torch.empty_like(dS)
+        # dL/dA = grad_scale * (dS + dS^T) A / T  (anchors and contrasts are the same tensor)
+        _lib.check(lib.cavp_symm_add(_ptr(dS), _ptr(G), npad, C.c_float(grad_scale / self.crit.temperature), st), "cavp_symm_add")
+        dA = T.zeros((npad, Cc), torch.float32, dev)
+        T.linear_wgrad(A, G, dA)
+        self.saved = (plan, idx, dA, A, norms)
+        return loss
+
+    def add_rows(self, g: torch.Tensor) -> bool:
+        """TrainPass.grad_tap function of the fusion map."""
+        if self.saved is None:
+            return False
+        plan, idx, dA, A, norms = self.saved
+        contrast_rows_bwd_add(g, plan, idx, dA, A, norms, 1.0)
+        return True

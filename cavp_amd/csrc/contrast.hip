@@ -399,6 +399,99 @@ __global__ __launch_bounds__(256) void l2norm_bwd_scatter_dev_kernel(const float
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The two ends of the chain on the training tape's fusion map as it lies in memory: x / g = [2B][HW][ld] of the compute dtype
+// (ld >= C, the match half first).  Anchor i lives in image idx_b[i] (i < n_match) or B + idx_b[i]; the count comes from the
+// device sampler's header or, header == nullptr, from the host.  One wave per anchor row, 16-byte vectors, f32 arithmetic.
+struct AnchorCount { int n, n_match; };
+__device__ __forceinline__ AnchorCount anchor_count(const int* __restrict__ header, int cap, int N, int n_match) {
+  if (!header) return {N, n_match};
+  int n = header[0];
+  n = n < 0 ? 0 : (n > cap ? cap : n);
+  return {n, header[1]};
+}
+// first element of anchor i's row, or -1 when the plan entry does not address a pixel of the map (rows >= n hold -1)
+__device__ __forceinline__ long long anchor_row(const int* __restrict__ ib, const int* __restrict__ ip, int i, int n_match, int B,
+                                                int HW, int ld) {
+  const int b = ib[i], p = ip[i];
+  if ((unsigned)b >= (unsigned)B || (unsigned)p >= (unsigned)HW) return -1;
+  return ((long long)(b + (i < n_match ? 0 : B)) * HW + p) * ld;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void contrast_gather_nhwc_kernel(const T* __restrict__ x, int B, int HW, int ld, int C,
+                                                                   const int* __restrict__ header, const int* __restrict__ ib,
+                                                                   const int* __restrict__ ip, int cap, int N, int n_match,
+                                                                   int rows, float eps, float* __restrict__ A,
+                                                                   float* __restrict__ norms) {
+  constexpr int VE = VecT<T>::VE;
+  const int lane = threadIdx.x & 63, CV = C / VE;
+  const AnchorCount cnt = anchor_count(header, cap, N, n_match);
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < rows; i += gridDim.x * 4) {
+    float* dst = A + (size_t)i * C;
+    const long long off = i < cnt.n ? anchor_row(ib, ip, i, cnt.n_match, B, HW, ld) : -1;
+    if (off < 0) {
+      for (int c = lane * 4; c < C; c += 256) *(float4*)(dst + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (lane == 0) norms[i] = 1.f;
+      continue;
+    }
+    const T* src = x + off;
+    float q = 0.f, v[VE];
+    for (int cv = lane; cv < CV; cv += 64) {
+      VecT<T>::load(src + cv * VE, v);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) q += v[e] * v[e];
+    }
+    const float nrm = fmaxf(sqrtf(wave_sum(q)), eps);
+    for (int cv = lane; cv < CV; cv += 64) {   // (the row is a few hundred bytes: the second read comes from the cache)
+      VecT<T>::load(src + cv * VE, v);
+#pragma unroll
+      for (int e = 0; e < VE; e += 4)
+        *(float4*)(dst + cv * VE + e) = make_float4(v[e] / nrm, v[e + 1] / nrm, v[e + 2] / nrm, v[e + 3] / nrm);
+    }
+    if (lane == 0) norms[i] = nrm;
+  }
+}
+
+// g_row += scale * (dA_i - A_i <A_i, dA_i>) / norms[i]; the anchors are distinct pixels per half: plain read-modify-write
+template <typename T>
+__global__ __launch_bounds__(256) void contrast_rows_bwd_add_kernel(T* __restrict__ g, int B, int HW, int ld, int C,
+                                                                    const int* __restrict__ header, const int* __restrict__ ib,
+                                                                    const int* __restrict__ ip, int cap, int N, int n_match,
+                                                                    const float* __restrict__ dA, const float* __restrict__ A,
+                                                                    const float* __restrict__ norms, float scale) {
+  constexpr int VE = VecT<T>::VE;
+  const int lane = threadIdx.x & 63, CV = C / VE;
+  const AnchorCount cnt = anchor_count(header, cap, N, n_match);
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < cnt.n; i += gridDim.x * 4) {
+    const long long off = anchor_row(ib, ip, i, cnt.n_match, B, HW, ld);
+    if (off < 0) continue;
+    const float* a = A + (size_t)i * C;
+    const float* d = dA + (size_t)i * C;
+    float dot = 0.f;
+    for (int c = lane * 4; c < C; c += 256) {
+      const float4 av = *(const float4*)(a + c), dv = *(const float4*)(d + c);
+      dot += av.x * dv.x + av.y * dv.y + av.z * dv.z + av.w * dv.w;
+    }
+    dot = wave_sum(dot);
+    const float inv = scale / norms[i];
+    T* dst = g + off;
+    for (int cv = lane; cv < CV; cv += 64) {
+      float v[VE];
+      VecT<T>::load(dst + cv * VE, v);
+#pragma unroll
+      for (int e = 0; e < VE; e += 4) {
+        const float4 av = *(const float4*)(a + cv * VE + e), dv = *(const float4*)(d + cv * VE + e);
+        v[e] += (dv.x - av.x * dot) * inv;
+        v[e + 1] += (dv.y - av.y * dot) * inv;
+        v[e + 2] += (dv.z - av.z * dot) * inv;
+        v[e + 3] += (dv.w - av.w * dot) * inv;
+      }
+      VecT<T>::store(dst + cv * VE, v);
+    }
+  }
+}
+
 }  // namespace
 
 // F.interpolate(mode='nearest') of the label maps to the feature resolution (contrastive_aud.py:18-22): source index
@@ -520,5 +613,46 @@ extern "C" int cavp_l2norm_bwd_scatter_dev(const float* dA, const float* A, cons
   l2norm_bwd_scatter_dev_kernel<<<(cap + 3) / 4, 256, 0, (hipStream_t)stream>>>(dA, A, norms, header, idx_b, idx_p, cap, C, dxm,
                                                                                 m_stride_b, m_stride_c, m_stride_p, dxs, s_stride_b,
                                                                                 s_stride_c, s_stride_p);
+  CHECK_LAUNCH();
+}
+
+// ---- the chain's two ends on the [2B][HW][ld] compute-dtype fusion map of the training tape ----
+// shared argument check: C a multiple of 8 (one 16-byte bf16 vector; f32 rows of A / dA then split into float4 as well), ld a
+// multiple of the dtype's vector, 16-byte aligned bases; the count from `header` (cap rows of plan) or from (N, n_match)
+static int contrast_nhwc_args_ok(int dtype, const void* x, int B, int HW, int ld, int C, const int32_t* header, const int32_t* idx_b,
+                                 const int32_t* idx_p, int cap, int N, int n_match, const float* a0, const float* a1,
+                                 const float* norms) {
+  if (!dt_ok(dtype) || !x || !idx_b || !idx_p || !a0 || !a1 || !norms || B <= 0 || HW <= 0 || C <= 0 || ld < C) return CAVP_ERR_BAD_ARG;
+  if (header ? cap <= 0 : (N <= 0 || n_match < 0 || n_match > N)) return CAVP_ERR_BAD_ARG;
+  if (C % 8 != 0 || ld % dt_ve(dtype) != 0) return CAVP_ERR_BAD_ARG;
+  if (!al16(x) || !al16(a0) || !al16(a1)) return CAVP_ERR_ALIGN;
+  return CAVP_OK;
+}
+
+extern "C" int cavp_contrast_gather_nhwc(int32_t dtype, const void* x, int32_t B, int32_t HW, int32_t ld, int32_t C,
+                                         const int32_t* header, const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t N,
+                                         int32_t n_match, int32_t rows, float eps, float* A, float* norms, void* stream) {
+  const int st = contrast_nhwc_args_ok(dtype, x, B, HW, ld, C, header, idx_b, idx_p, cap, N, n_match, A, A, norms);
+  if (st != CAVP_OK) return st;
+  if (rows < (header ? cap : N)) return CAVP_ERR_BAD_ARG;
+  cavp_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    contrast_gather_nhwc_kernel<T><<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>((const T*)x, B, HW, ld, C, header, idx_b, idx_p, cap, N,
+                                                                                   n_match, rows, eps, A, norms);
+  });
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_contrast_rows_bwd_add(int32_t dtype, void* g, int32_t B, int32_t HW, int32_t ld, int32_t C, const int32_t* header,
+                                          const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match,
+                                          const float* dA, const float* A, const float* norms, float scale, void* stream) {
+  const int st = contrast_nhwc_args_ok(dtype, g, B, HW, ld, C, header, idx_b, idx_p, cap, N, n_match, dA, A, norms);
+  if (st != CAVP_OK) return st;
+  const int rows = header ? cap : N;
+  cavp_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    contrast_rows_bwd_add_kernel<T><<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>((T*)g, B, HW, ld, C, header, idx_b, idx_p, cap, N,
+                                                                                    n_match, dA, A, norms, scale);
+  });
   CHECK_LAUNCH();
 }

@@ -1037,6 +1037,33 @@ class TrainPass:
         self.tape.append(bwd)
         return y
 
+    def grad_tap(self, x: V, fn: Callable[[torch.Tensor], Optional[bool]]) -> V:
+        """Identity in the forward.  In the backward, once every consumer recorded after this call has contributed to x.g,
+        fn(g) adds a further (typically sparse) gradient into `g` in place; it returns False when it had nothing to add.  Follows
+        acc()'s rules: the add goes into a copy while a deferred weight gradient still reads x.g, and the by-products of the
+        launch that wrote x.g (g_scaled, bnb_part) are dropped once x.g has changed."""
+        self._use(x)
+        if x.parent is not None:
+            raise CavpError("a gradient tap on a slice is not supported")
+
+        def bwd():
+            if not x.needs_grad:
+                return
+            g = x.g
+            if g is None:
+                g = T.zeros(x.t.shape, x.t.dtype, self.dev)
+            elif self._pinned(g) or not g.is_contiguous():
+                g = self._dense_copy(g)
+            wrote = fn(g) is not False
+            if g is not x.g:
+                if wrote:
+                    x.set_g(g)
+            elif wrote:
+                x.g_scaled = None
+                x.bnb_part = None
+        self.tape.append(bwd)
+        return x
+
     def mark_early_grads_final(self) -> None:
         """Tape marker: everything recorded AFTER this point in the forward (audio encoder, projector, cross attention,
         decoder head) has its parameter gradients complete when the backward reaches it."""
@@ -1214,9 +1241,11 @@ def _head_stage(tp: TrainPass, m, fusion: V) -> V:
     return lo
 
 
-def run_train_forward(model, image: torch.Tensor, audio: torch.Tensor, tp: TrainPass, shuffle=None):
+def run_train_forward(model, image: torch.Tensor, audio: torch.Tensor, tp: TrainPass, shuffle=None, fusion_tap=None):
     """Mirrors CAVP._forward_hip (eval) op by op with batch-statistics BN and a backward tape.  Returns the V's of
-    (logits_lowres, fusion NHWC, fea_v_proj NHWC, fea_a, attn)."""
+    (logits_lowres, fusion NHWC, fea_v_proj NHWC, fea_a, attn).
+    fusion_tap: a TrainPass.grad_tap function for the fusion map, recorded between the fusion stage and the head: in the backward
+    it runs after head0's data gradient and before the fusion stage's (the contrastive term of the native step enters there)."""
     from .cavp_model import VGG
     m = model
     pvt = m.seg_model == "PVT"
@@ -1355,6 +1384,8 @@ def run_train_forward(model, image: torch.Tensor, audio: torch.Tensor, tp: Train
     if shuffle is not None:   # forward_audio (cavp_model.py:156-173): features | the same features gathered by shuffle_idx
         fea_a = tp.gather_cat(fea_a, model._bank_and_shuffle(fea_a.t, shuffle[0], shuffle[1]))
     fusion, fea_v_proj, attn = _fusion_stage(tp, m, fea_v, fea_a, duplicate=True)
+    if fusion_tap is not None:
+        tp.grad_tap(fusion, fusion_tap)
     lo = _head_stage(tp, m, fusion)
     tp.named.update(fea_v=fea_v, f4=f4, f1=f1, fea_a=fea_a, asp=asp, cat=cat, zcat=zcat)
     if tp._nbt:

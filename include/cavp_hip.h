@@ -501,6 +501,22 @@ int cavp_l2norm_bwd_scatter_dev(const float* dA, const float* A, const float* no
                                 int64_t m_stride_p, float* dxs, int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p,
                                 void* stream);
 
+/* ---- The two ends of the chain on the training tape's fusion map (two entry points added to ABI 15; nothing else changed) ----
+ * x / g: the map as it lies in memory, [2B][HW][ld] of `dtype` (CAVP_F32 / CAVP_BF16), ld >= C, the match half first.  Anchor row i
+ * addresses image idx_b[i] (i < n_match) or B + idx_b[i] (i >= n_match), pixel idx_p[i].  The anchor count comes from `header`
+ * (the device sampler's, cap = the plan's capacity) or, header == NULL, from (N, n_match).  One wave per row, 16-byte vectors,
+ * f32 arithmetic.  C % 8 == 0 and ld a multiple of the 16-byte vector, else CAVP_ERR_BAD_ARG; x / g / A / dA 16-byte aligned.
+ * A plan entry outside [0, B) x [0, HW) counts as a row >= n. */
+/* A[i] = x_row / max(||x_row||_2, eps) as f32 [rows][C] + norms[i]; rows (>= cap resp. N): rows >= n are zero with norm 1. */
+int cavp_contrast_gather_nhwc(int32_t dtype, const void* x, int32_t B, int32_t HW, int32_t ld, int32_t C, const int32_t* header,
+                              const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match, int32_t rows,
+                              float eps, float* A, float* norms, void* stream);
+/* g_row += scale * (dA_i - A_i <A_i, dA_i>) / norms[i], read-modify-write in `dtype`, no atomics: the anchors must be distinct
+ * pixels per half (both samplers pick without replacement).  Rows outside the plan and channels >= C are not touched. */
+int cavp_contrast_rows_bwd_add(int32_t dtype, void* g, int32_t B, int32_t HW, int32_t ld, int32_t C, const int32_t* header,
+                               const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match, const float* dA,
+                               const float* A, const float* norms, float scale, void* stream);
+
 /* ---- PVTv2-B5 visual backbone (models/visual/backbones/pvt/pvt.py, config #4 / SURVEY.md §8a row a12) ---- */
 /* Attention.forward (pvt.py:102-130): softmax(q k^T * scale) v per head with the spatially-reduced K/V (Nk <= 256,
  * head_dim 64).  q, o: [B][Nq][heads*64]; kv: [B][Nk][2*heads*64] (k then v, as written by the `kv` Linear). */

@@ -11,6 +11,10 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
+                                   [--contrast [--contrast-weight W]]
+
+--contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
+ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
 """
 import argparse
 import os
@@ -40,6 +44,9 @@ def main():
     ap.add_argument("--seg-model", choices=["DeepLabV3Plus", "PVT"], default="DeepLabV3Plus", help="PVT = config #4's PVTv2-B5 backbone")
     ap.add_argument("--fixed-batch", action="store_true", help="train on ONE batch (over-fit sanity: the loss must fall)")
     ap.add_argument("--from-waveform", action="store_true", help="start from 16 kHz waveforms (HIP log-mel front-end)")
+    ap.add_argument("--contrast", action="store_true", help="add the pixel-level contrastive term to the native step (device sampler)")
+    ap.add_argument("--contrast-weight", type=float, default=1.0, help="W in l_ce + W * l_ctr (the reference's args.loss_w)")
+    ap.add_argument("--max-views", type=int, default=512)
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -66,6 +73,10 @@ def main():
     model.train().to(dev).set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
     sched = warmup_poly_lr(a.lr, a.lr_power, a.total_iters, 0)
     front = MelFrontEnd(hyp, device=dev) if a.from_waveform else None
+    crit = None
+    if a.contrast:
+        from cavp_amd.contrast import ContrastLoss
+        crit = ContrastLoss(0.1, 255, a.max_views).use_device_sampler(min(max(a.num_classes - 1, 1), 254), seed=1234 + rank)
 
     g = torch.Generator().manual_seed(1234 + rank)
     B = a.batch
@@ -82,7 +93,12 @@ def main():
             audio = front(wave)
         else:
             audio = (torch.rand(2 * B, 1, 96, 64, generator=g) * 2 - 1).to(dev)
-        loss = model.train_step(image, audio, label)
+        if crit is not None:
+            shuf = label.clone()
+            shuf[B // 2:] = 0
+            loss = model.train_step(image, audio, label, contrast=crit, label_shuffle=shuf, contrast_weight=a.contrast_weight)
+        else:
+            loss = model.train_step(image, audio, label)
         if opt is None:
             opt = FusedSGDAdam(model, model._grad_arena, a.lr, momentum=a.momentum, weight_decay=a.weight_decay)
         # the reference sets the learning rate AFTER the optimiser step (trainer_cavp_vpo_mono.py:193-203): step `it` runs with
@@ -94,7 +110,8 @@ def main():
         if first is None:
             first = float(loss.item())
         if rank == 0 and (it % 5 == 0 or it == a.steps - 1):
-            print(f"iter {it:4d}  lr {sched(it):.3e}  loss {float(loss.item()):.4f}", flush=True)
+            terms = "  (CE {:.4f}, contrast {:.4f})".format(*(float(t.item()) for t in model._last_losses)) if crit is not None else ""
+            print(f"iter {it:4d}  lr {sched(it):.3e}  loss {float(loss.item()):.4f}{terms}", flush=True)
     torch.cuda.synchronize()
     if rank == 0 and t0 is not None and a.steps > 2:
         dt = (time.time() - t0) / (a.steps - 2)
