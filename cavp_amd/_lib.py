@@ -164,6 +164,11 @@ PROTOTYPES = {
     # ---- mask / probability / confusion counts from the low-resolution logits (ABI 15) ----
     "cavp_seg_predict_nhwc": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i64,
                                      _vp, _vp]),
+    # ---- pair builder: shuffle, overwrite, sound bank (added to ABI 15) ----
+    "cavp_pairs_plan": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_pairs_gather": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "cavp_pairs_bank_update": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "cavp_pairs_labels": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
 }
 
 _lib = None

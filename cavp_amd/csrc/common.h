@@ -284,6 +284,24 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// 64-bit sort key of the counter-based draws (contrast.hip's anchor sampler, pairs.hip's shuffle): (r0 << 32) | r1 of
+// r = Philox4x32-10(counter = (c0, c1, c2, c3), key = (k0, k1)) (Salmon et al., SC'11).
+__device__ __forceinline__ unsigned long long philox_key(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                                         unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1;
+    c3 = (unsigned)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return ((unsigned long long)c0 << 32) | c1;
+}
+
 // floor(n / d) for 0 <= n < 2^31 by a host-prepared multiplier: m = floor(2^(31+L) / d) + 1, L = ceil(log2 d), shift = 31 + L
 // (exact: the error term n * e / 2^(31+L), e <= 1, stays below 1/d because n < 2^31 <= 2^(31+L) / d).  The tile set-up did
 // two real integer divisions per operand row (~40 VALU each, 8 per thread and tile): ~1 us of every tile at 2 waves per SIMD.

@@ -149,21 +149,7 @@ constexpr int kSelThreads = 1024;
 constexpr int kSelBits = 12;          // radix digit of the threshold search
 constexpr int kSelList = 2048;        // candidates sorted in LDS: < max_views <= 1024 below the boundary digit + <= 1024 inside it
 
-__device__ __forceinline__ unsigned long long philox_key(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                                         unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1;
-    c3 = (unsigned)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return ((unsigned long long)c0 << 32) | c1;
-}
+// (philox_key: common.h, shared with pairs.hip)
 
 __global__ __launch_bounds__(256) void contrast_count_kernel(const int* __restrict__ gm, long long total, int* __restrict__ partial) {
   __shared__ unsigned hist[kHistStride];

@@ -616,6 +616,45 @@ int cavp_seg_predict_nhwc(int32_t dtype, const void* x, int32_t N, int32_t Hi, i
                           int32_t Wo, int32_t align_corners, uint8_t* mask, float* prob, int32_t channel, const void* labels,
                           int32_t label_dtype, int32_t K, int64_t ignore, uint64_t* M, void* stream);
 
+/* ---- Pair builder (four entry points added to ABI 15; nothing else changed): the mismatched audio-visual pairs of the reference
+ * trainers (trainer_cavp_vpo_mono.py:87-115,148-181, SoundBank in models/cavp_model.py:21-52) without the host ----
+ * A batch of B mono clips waveform [B][A] f32 with image labels img_label [B][K] i64 (multi-hot in {0, 1}, column 0 = background)
+ * and a per-class FIFO of clips kept as a ring: bank [K][S][A] f32 + head int32[K], logical slot j = physical (head + j) % S,
+ * slot 0 the oldest; a zeroed bank with zero heads is the empty FIFO.  Launch order on one stream: plan, gather, bank_update,
+ * labels.  gather must precede bank_update: the slot an overwritten row reads is the one a push to that class replaces.
+ *
+ * cavp_pairs_plan (one workgroup; B <= 1024, K <= 256):
+ *   perm[j] = the row with the j-th smallest (key, i), key of row i = (r0 << 32) | r1 of Philox4x32-10(counter = (i, stream,
+ *   offset_lo, offset_hi), key = (seed_lo, seed_hi)), stream 0; perm_in (int32[B], optional) replaces the draw.
+ *   if_match[i] = all_k(img_label[i][k] == img_label[perm[i]][k]).  With overwrite != 0: of the n_false rows with if_match == 0
+ *   the q = ow_table[n_false] with the smallest (rank, i) are picked (rank = the stream-1 key, or rank_in int32[B] >= 0); a picked
+ *   row with exactly one non-zero non-background label c becomes a match: if_match = 1, img_label_shuffle[i] = img_label[i],
+ *   source[i] = ~c, its clip = logical slot 0 of class c BEFORE this step's pushes.  Every other row: img_label_shuffle[i] =
+ *   img_label[perm[i]], source[i] = perm[i].  Then, rows ascending, a row with exactly one non-zero non-background label c pushes
+ *   its clip at the end of class c's FIFO; of more than S pushes to one class only the last S are written.
+ *   ow_table int32[ow_table_len], ow_table_len > B: the host's int(n * ow_rate) for n = 0 .. (no float arithmetic on the device).
+ *   state  int64[4] (device, persistent): {seed, offset, bad_inputs, reserved}; a call reads seed / offset, then offset += 1 and
+ *          bad_inputs += the img_label entries outside {0, 1} (taken as "non-zero") + the perm_in entries outside [0, B)
+ *          (replaced by the identity): no input value makes a kernel read or write out of bounds.
+ *   header int32[8]: {n_false, q, rows overwritten, rows written to the bank, offset_lo, offset_hi, seed_lo, seed_hi}.
+ *   src_table int32[2B]: row r of the 2B-clip output comes from waveform row e (e >= 0) or from physical bank slot ~e of the
+ *          flattened [K*S] slots (e < 0); the first B entries are 0 .. B-1.  wr_table int32[B]: the physical slot row r is
+ *          written to, or -1.  The plan kernel is the only reader and writer of `head`.
+ * cavp_pairs_gather: out [2B][A] from src_table.  cavp_pairs_bank_update: the writer rows into their slots.  Both use 16-byte
+ *   accesses when A % 4 == 0 and every base is 16-byte aligned, 4-byte accesses otherwise.
+ * cavp_pairs_labels: label_shuffle[i] = if_match[i] ? pix_label[i] : 0 over HW i64 per row (16-byte accesses when HW % 2 == 0
+ *   and both bases are aligned); unmatched rows are written without a read.
+ * No allocation, no synchronisation, no host read of a device value: the four launches are capturable in a hipGraph. */
+int cavp_pairs_plan(const int64_t* img_label, int32_t B, int32_t K, int32_t S, const int32_t* perm_in, const int32_t* rank_in,
+                    int32_t overwrite, const int32_t* ow_table, int32_t ow_table_len, int64_t* state, int32_t* head,
+                    int32_t* header, int32_t* perm, uint8_t* if_match, int64_t* img_label_shuffle, int32_t* source,
+                    int32_t* src_table, int32_t* wr_table, void* stream);
+int cavp_pairs_gather(const float* waveform, const float* bank, const int32_t* src_table, int32_t B, int32_t K, int32_t S, int32_t A,
+                      float* out, void* stream);
+int cavp_pairs_bank_update(const float* waveform, const int32_t* wr_table, int32_t B, int32_t K, int32_t S, int32_t A, float* bank,
+                           void* stream);
+int cavp_pairs_labels(const int64_t* pix_label, const uint8_t* if_match, int32_t B, int64_t HW, int64_t* label_shuffle, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

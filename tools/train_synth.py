@@ -11,10 +11,14 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
-                                   [--contrast [--contrast-weight W]]
+                                   [--contrast [--contrast-weight W]] [--pairs]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
+
+--pairs (with --from-waveform --contrast): the mismatched pairs are built as the reference trainers build them
+(trainer_cavp_vpo_mono.py:148-181), on the device: B clips and synthetic multi-hot image labels go through cavp_amd.pairs.PairBuilder
+(shuffle, overwrite from the sound bank from step 1 on, bank update), its 2B clips through MelFrontEnd, its label_shuffle into the step.
 """
 import argparse
 import os
@@ -47,7 +51,11 @@ def main():
     ap.add_argument("--contrast", action="store_true", help="add the pixel-level contrastive term to the native step (device sampler)")
     ap.add_argument("--contrast-weight", type=float, default=1.0, help="W in l_ce + W * l_ctr (the reference's args.loss_w)")
     ap.add_argument("--max-views", type=int, default=512)
+    ap.add_argument("--pairs", action="store_true", help="build the shuffled half of the batch and its labels with PairBuilder")
+    ap.add_argument("--ow-rate", type=float, default=0.5, help="share of the mismatched rows overwritten from the sound bank")
     a = ap.parse_args()
+    if a.pairs and not (a.from_waveform and a.contrast):
+        ap.error("--pairs needs --from-waveform and --contrast")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -78,6 +86,13 @@ def main():
         from cavp_amd.contrast import ContrastLoss
         crit = ContrastLoss(0.1, 255, a.max_views).use_device_sampler(min(max(a.num_classes - 1, 1), 254), seed=1234 + rank)
 
+    pairs = None
+    if a.pairs:
+        from cavp_amd.pairs import PairBuilder
+        K = max(a.num_classes, 2)
+        pairs = PairBuilder(num_classes=K, bank_slots=a.batch, wave_len=16000, ow_rate=a.ow_rate, seed=1234 + rank, device=dev,
+                            max_batch=a.batch)
+
     g = torch.Generator().manual_seed(1234 + rank)
     B = a.batch
     opt = None
@@ -88,12 +103,25 @@ def main():
             g = torch.Generator().manual_seed(1234 + rank)      # the same batch every step
         image = torch.randn(B, 3, a.hw, a.hw, generator=g).to(dev)
         label = torch.randint(0, a.num_classes, (B, a.hw, a.hw), generator=g).to(dev)
-        if front is not None:                                   # matched clips ‖ shuffled clips = 2B (cavp_model.py:181)
+        built = None
+        if pairs is not None:                                   # B clips + image labels -> matched ‖ shuffled clips, shuffle labels
+            wave = (torch.randn(B, 1, 16000, generator=g) * 0.1).to(dev)
+            img_label = torch.zeros(B, pairs.K, dtype=torch.int64)
+            img_label[torch.arange(B), torch.randint(1, pairs.K, (B,), generator=g)] = 1       # one source per frame ...
+            two = torch.rand(B, generator=g) < 0.25                                             # ... a second one for a quarter
+            img_label[two, torch.randint(1, pairs.K, (int(two.sum()),), generator=g)] = 1
+            img_label[:, 0] = torch.randint(0, 2, (B,), generator=g)
+            built = pairs(wave, label, img_label.to(dev), overwrite=it >= 1)
+            audio = front(built.waveforms)
+        elif front is not None:                                 # matched clips ‖ shuffled clips = 2B (cavp_model.py:181)
             wave = (torch.randn(2 * B, 1, 16000, generator=g) * 0.1).to(dev)
             audio = front(wave)
         else:
             audio = (torch.rand(2 * B, 1, 96, 64, generator=g) * 2 - 1).to(dev)
-        if crit is not None:
+        if built is not None:
+            loss = model.train_step(image, audio, label, contrast=crit, label_shuffle=built.label_shuffle,
+                                    contrast_weight=a.contrast_weight)
+        elif crit is not None:
             shuf = label.clone()
             shuf[B // 2:] = 0
             loss = model.train_step(image, audio, label, contrast=crit, label_shuffle=shuf, contrast_weight=a.contrast_weight)
@@ -117,6 +145,10 @@ def main():
         dt = (time.time() - t0) / (a.steps - 2)
         print(f"{B * world / dt:.1f} frames/s over {world} GPU(s) ({dt * 1e3:.1f} ms/step incl. host-side input generation, "
               f"eager launches, optimiser step)")
+    if rank == 0 and pairs is not None:
+        plan = pairs.last_plan()
+        print(f"pairs, last step: {int(plan['if_match'].sum())} of {B} rows matched, {plan['n_overwritten']} taken from the sound bank "
+              f"(q = {plan['q']} of {plan['n_false']} mismatched), {plan['n_written']} clips queued")
     if rank == 0 and a.fixed_batch:
         print(f"fixed batch: loss {first:.4f} -> {float(loss.item()):.4f} after {a.steps} steps")
     if world > 1:
