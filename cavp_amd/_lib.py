@@ -90,6 +90,10 @@ PROTOTYPES = {
     "cavp_optimizer_blocks": (_i32, [C.c_int64]),
     "cavp_optimizer_step": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_int64, _vp]),
+    # device-resident schedule: step counter, poly learning rate and bias corrections on the GPU (added to ABI 15)
+    "cavp_optimizer_state_bytes": (C.c_int64, []),
+    "cavp_optimizer_schedule": (_i32, [_vp, _vp]),
+    "cavp_optimizer_step_dev": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp]),
     "cavp_mel_frontend": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp]),
     "cavp_unpack_weight_grad": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_conv3x3_smallcin_wgrad": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),

@@ -844,6 +844,21 @@ class CAVP(nn.Module):
             return (H - 1) // 4 + 1, (W - 1) // 4 + 1                         # 7 x 7 patch embedding, stride 4, pad 3
         return ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1             # 3 x 3 stem conv stride 2 pad 1, 3 x 3 max-pool stride 2 pad 1
 
+    def grad_arena(self, device):
+        """The flat f32 gradient arena of the native training step on `device` (created on first use; train_step calls this).  An
+        optimiser that a captured step is to record (FusedSGDAdam) is built on it, which this allows before any step has run."""
+        from .train import GradArena
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        arena = getattr(self, "_grad_arena", None)
+        if arena is None or arena.flat.device != device:
+            big = {id(m.weight) for m in self.modules() if isinstance(m, (nn.Linear, nn.Conv2d))
+                   and m.weight.numel() >= _GRAD_OVERWRITE_MIN} if _GRAD_OVERWRITE_MIN > 0 else set()
+            arena = self._grad_arena = GradArena(list(self.parameters()), device, late_ids=self._late_grad_ids(),
+                                                 no_zero_ids=big)
+        return arena
+
     def train_step(self, image, audio, label, ignore_index: int = 255, loss_scale: float = 1.0, all_reduce: bool = True,
                    _split_hook=None, want_pred: bool = False, contrast=None, label_shuffle=None, contrast_weight: float = 1.0):
         """MI355X-native fused training step (no torch.autograd): forward_train (batch-stat BN, audio 2B) -> HIP
@@ -861,16 +876,11 @@ class CAVP(nn.Module):
         required; `self._last_losses = (l_ce, l_ctr)`, both unweighted 1-element device tensors.
         Returns the (local) loss as a 1-element device tensor."""
         from . import train_ops as T
-        from .train import (GradArena, TrainPass, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world,
+        from .train import (TrainPass, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world,
                             run_train_forward)
         if not image.is_cuda:
             raise CavpError("CAVP (MI355X path) needs inputs on a HIP device: there is no CPU fallback")
-        arena = getattr(self, "_grad_arena", None)
-        if arena is None or arena.flat.device != image.device:
-            big = {id(m.weight) for m in self.modules() if isinstance(m, (nn.Linear, nn.Conv2d))
-                   and m.weight.numel() >= _GRAD_OVERWRITE_MIN} if _GRAD_OVERWRITE_MIN > 0 else set()
-            arena = self._grad_arena = GradArena(list(self.parameters()), image.device, late_ids=self._late_grad_ids(),
-                                                 no_zero_ids=big)
+        arena = self.grad_arena(image.device)
         term = None
         if contrast is not None:
             from .contrast import ContrastLoss, NativeContrastTerm
@@ -925,7 +935,8 @@ class CAVP(nn.Module):
         return loss
 
     def capture_train_step(self, image, audio, label, ignore_index: int = 255, loss_scale: float = 1.0,
-                           split: Optional[bool] = None, contrast=None, label_shuffle=None, contrast_weight: float = 1.0):
+                           split: Optional[bool] = None, contrast=None, label_shuffle=None, contrast_weight: float = 1.0,
+                           optimizer=None, prologue=None):
         """Capture forward_train + CE + backward (about 1000 kernel launches) into hipGraphs and return
         `replay() -> loss`.  `image`, `audio`, `label` are the static input buffers: copy new batches into them before
         each replay.  Weight packing is part of the graph, so replays always see the current parameters.
@@ -934,8 +945,35 @@ class CAVP(nn.Module):
         concurrently with the collective) -> all-reduce of the late range -> join.
         contrast / label_shuffle / contrast_weight as in train_step (`label_shuffle` is a static input buffer too).  The criterion
         must use the device sampler (ContrastLoss.use_device_sampler): its call counter lives on the device, so every replay draws
-        fresh anchors, and `contrast.manual_seed()` between replays restarts the sequence.  All contrast launches are in graph 1."""
+        fresh anchors, and `contrast.manual_seed()` between replays restarts the sequence.  All contrast launches are in graph 1.
+        optimizer: a FusedSGDAdam with the device schedule (use_device_schedule) built on this model's gradient arena
+        (`self.grad_arena(device)`).  Its update is recorded in the captured pass only - the two warm-up passes and the capture itself leave
+        the weights and its step counter alone - as the last launches of the last graph: on the capture stream after train_step
+        has returned, that is after every side and branch stream has been joined into it and after the tape's last launch
+        (finish_padded), so no gradient is still being written when the update reads the arena.  A replay is then forward +
+        backward + update at the next step of the schedule.  With collectives on the all-reduce runs between the graphs and
+        the host, so the update cannot be in a graph: replay() issues optimizer.step() behind the late all-reduce instead
+        (no synchronisation either).  `p.grad` stay valid after a replay, and one optimiser may be recorded in several graphs
+        (they share its device state).
+        prologue: a callable run first in each of the three passes (two warm-ups, the capture) on that pass's stream; it writes
+        the static `audio` / `label_shuffle` buffers, which puts the input pipeline into the same graph:
+            def prologue():
+                built = pairs(wave, label, img_label, overwrite, out=built0)
+                audio.copy_(front(built.waveforms)); shuf.copy_(built.label_shuffle)
+        The warm-up passes run it for real: a PairBuilder's and the device sampler's call counters (and the sound bank) have
+        advanced by three calls when this returns - reseed (`manual_seed`) after the capture."""
         from .train import _no_gc_during_capture, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world
+        if optimizer is not None:
+            if getattr(optimizer, "_sched", None) is None:
+                raise CavpError("capture_train_step: only an optimiser with the device schedule can be recorded "
+                                "(FusedSGDAdam.use_device_schedule); step(lr) would freeze the captured rate and step count")
+            if getattr(self, "_grad_arena", None) is None or optimizer._arena is not self._grad_arena \
+                    or self._grad_arena.flat.device != image.device:
+                raise CavpError("capture_train_step: the optimiser was not built on this model's gradient arena")
+        if prologue is not None and not callable(prologue):
+            raise CavpError("capture_train_step: prologue must be callable")
+        opt_in_graph = optimizer is not None and not collectives_on()
+        pro = prologue if prologue is not None else (lambda: None)
         if contrast is not None and getattr(contrast, "_dev", None) is None:
             raise CavpError("capture_train_step: the contrast term can only be captured with the device sampler "
                             "(ContrastLoss.use_device_sampler); the host sampler reads the labels and draws on the CPU every step")
@@ -944,18 +982,23 @@ class CAVP(nn.Module):
         if split is None:
             split = collectives_on()
         with torch.no_grad():
+            pro()
             self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)   # warm-up: workspace, arena
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
+                pro()
                 self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)
             torch.cuda.current_stream().wait_stream(side)
             if not split:
                 graph = torch.cuda.CUDAGraph()
                 # thread_local: other threads (RCCL's watchdog polls its events) must not invalidate the capture
                 with _no_gc_during_capture(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    pro()
                     loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False, **ctr)
+                    if opt_in_graph:
+                        optimizer.step()   # last on the capture stream: every branch has been joined by now
                 graphs = (graph,)
             else:
                 g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -969,8 +1012,11 @@ class CAVP(nn.Module):
                         g1.capture_end()
                         g2.capture_begin(pool=g1.pool(), capture_error_mode="thread_local")   # shares (and keeps alive) graph 1's allocations
 
+                    pro()
                     loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False,
                                            _split_hook=cut, **ctr)
+                    if opt_in_graph:
+                        optimizer.step()
                     g2.capture_end()
                 torch.cuda.current_stream().wait_stream(cap)
                 graphs = (g1, g2)
@@ -988,6 +1034,8 @@ class CAVP(nn.Module):
                 allreduce_arena_late(arena, work)
             elif collectives_on():
                 allreduce_arena_late(arena, None)
+            if optimizer is not None and not opt_in_graph:
+                optimizer.step()   # the all-reduce is outside the graphs, so the update is too: eager, behind it on the stream
             return loss
         # keep alive: the graphs, and every scratch buffer whose address they baked in (ops.workspace never frees a buffer it
         # has handed out, see there)

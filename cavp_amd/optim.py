@@ -11,11 +11,15 @@ and a warm-up + polynomial learning-rate schedule (engine/lr_policy.py:30-43, tr
 Because `cavp_amd.cavp_model.CAVP` keeps the reference's module tree, those torch optimisers work on it unchanged.  This
 module is the fused alternative for `CAVP.train_step`: every parameter is updated by ONE kernel launch
 (`cavp_optimizer_step`) straight from the flat gradient arena, with a device-resident job table built once.
+
+`FusedSGDAdam.use_device_schedule(...)` moves the step counter and the schedule to the GPU as well (struct cavp_opt_state):
+`step()` is then two launches that take nothing from the host, and `CAVP.capture_train_step(optimizer=...)` records them at
+the end of the training graph.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, Dict, List
+from typing import Callable, Dict, List, Optional
 
 import torch
 import torch.nn as nn
@@ -82,17 +86,30 @@ class OptJob(C.Structure):
                 ("vec", C.c_int32), ("pad_", C.c_int32)]
 
 
+class OptState(C.Structure):
+    """struct cavp_opt_state (include/cavp_hip.h)."""
+    _fields_ = [("t", C.c_int64), ("total_iters", C.c_int64), ("warmup_steps", C.c_int64), ("start_lr", C.c_double),
+                ("lr_power", C.c_double), ("end_lr", C.c_double), ("base_lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("lr_sgd", C.c_float), ("lr_adam", C.c_float), ("bc1", C.c_float),
+                ("bc2_sqrt", C.c_float), ("first_step", C.c_int32)]
+
+
 class FusedSGDAdam:
     """SGD(momentum, weight_decay) on `set_group_lr(model)` + Adam(lr = base lr) on `model.audio_backbone`, fused.
 
     `arena` is the model's flat gradient arena (`CAVP.train_step` creates it; gradients are its views).  `step(lr)`
     takes the current learning rate of the poly schedule: the visual groups use lr x {1, 10} (trainer lr_step), the
-    audio Adam keeps the constant base lr (trainer_cavp_vpo_mono.py:84 only logs it)."""
+    audio Adam keeps the constant base lr (trainer_cavp_vpo_mono.py:84 only logs it).
+
+    After `use_device_schedule(...)` the step count, the schedule and Adam's bias corrections live on the device: `step()`
+    takes no argument, reads nothing back and can be recorded in a hipGraph (CAVP.capture_train_step(optimizer=...))."""
 
     def __init__(self, model, arena, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4,
                  use_baseline: bool = False, betas=(0.9, 0.999), eps: float = 1e-8):
         self.base_lr, self.momentum, self.betas, self.eps = float(lr), float(momentum), betas, float(eps)
-        self.steps = 0
+        self._steps = 0
+        self._arena = arena          # capture_train_step checks that the optimiser reads the capturing model's arena
+        self._sched = None           # device cavp_opt_state (uint8 tensor) once use_device_schedule() was called
         import weakref
         self._model = weakref.ref(model) if hasattr(model, "params_changed") else (lambda: None)
         dev = arena.flat.device
@@ -137,21 +154,92 @@ class FusedSGDAdam:
         self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)   # device-resident job table
         self.params = [s[0] for s in specs]
 
-    def step(self, lr: float) -> None:
-        self.steps += 1
+    # ---- device-resident schedule ----------------------------------------------------------------------------------------
+    def use_device_schedule(self, start_lr: float, lr_power: float, total_iters: int, warmup_steps: int = 0,
+                            end_lr: float = 1e-8) -> "FusedSGDAdam":
+        """Keep the step counter t, the warm-up + poly schedule (`warmup_poly_lr` with these arguments) and Adam's bias
+        corrections on the device.  Step t runs with the configured rate for t == 0 and with get_lr(t - 1) afterwards (the
+        reference sets the rate after the step, trainer_cavp_vpo_mono.py:193-203); get_lr(i) for i >= total_iters, where the
+        host function has no value, is `end_lr`.  The counter starts at the number of steps taken so far."""
+        if int(total_iters) < 1 or int(warmup_steps) < 0:
+            raise _lib.CavpError("use_device_schedule: total_iters >= 1 and warmup_steps >= 0 required")
+        lib = _lib.load()
+        if lib.cavp_optimizer_state_bytes() != C.sizeof(OptState):
+            raise _lib.CavpError("use_device_schedule: struct cavp_opt_state of the library and OptState differ in size")
+        b1, b2 = self.betas
+        host = OptState(t=self._steps, total_iters=int(total_iters), warmup_steps=int(warmup_steps), start_lr=float(start_lr),
+                        lr_power=float(lr_power), end_lr=float(end_lr), base_lr=self.base_lr, beta1=b1, beta2=b2,
+                        lr_sgd=float(start_lr), lr_adam=self.base_lr, bc1=1.0, bc2_sqrt=1.0, first_step=0)
+        self._sched = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.state_m.device)
+        self._t_view = self._sched[OptState.t.offset:OptState.t.offset + 8].view(torch.int64)
+        self._lr_view = self._sched[OptState.lr_sgd.offset:OptState.lr_sgd.offset + 4].view(torch.float32)
+        return self
+
+    @property
+    def steps(self) -> int:
+        """Completed steps.  With the device schedule this is `iteration()` and synchronises."""
+        return self.iteration() if self._sched is not None else self._steps
+
+    @steps.setter
+    def steps(self, n: int) -> None:
+        if self._sched is not None:
+            self.set_iteration(n)
+        else:
+            self._steps = int(n)
+
+    def _need_sched(self, what: str):
+        if self._sched is None:
+            raise _lib.CavpError(f"FusedSGDAdam.{what} needs the device schedule (use_device_schedule)")
+
+    def last_lr(self) -> torch.Tensor:
+        """1-element f32 device view of the SGD rate of the most recent step (the rate of the start before the first one).
+        A trainer logs lr_bkb = lr_attn = lr, lr_seg = 10 lr and lr_audio = base_lr from it when it chooses to synchronise."""
+        self._need_sched("last_lr()")
+        return self._lr_view
+
+    def iteration(self) -> int:
+        """t, the number of completed steps, read from the device: synchronises, so never call it during a capture."""
+        self._need_sched("iteration()")
+        return int(self._t_view.item())
+
+    def set_iteration(self, t: int) -> None:
+        """Host-to-device write of t.  Like ContrastLoss.manual_seed it is not legal during a capture, nor while a graph that
+        uses the state is replaying; graphs captured earlier see the new value on their next replay."""
+        self._need_sched("set_iteration()")
+        if int(t) < 0:
+            raise _lib.CavpError("set_iteration: t >= 0 required")
+        self._t_view.copy_(torch.tensor([int(t)], dtype=torch.int64))
+
+    def step(self, lr: Optional[float] = None) -> None:
+        """One update from the arena's gradients.  `step(lr)` takes the rate of the host schedule; with the device schedule
+        `step()` issues the schedule launch and the update launch on the current stream and reads nothing back."""
+        if self._sched is not None and lr is not None:
+            raise _lib.CavpError("FusedSGDAdam.step(lr): the schedule lives on the device (use_device_schedule); call step()")
+        if self._sched is None and lr is None:
+            raise _lib.CavpError("FusedSGDAdam.step(): no learning rate; pass step(lr) or call use_device_schedule() first")
         if self._model() is not None:
             self._model().params_changed()   # weights change through raw pointers: no tensor version is bumped
+        if self._sched is not None:
+            lib, st = _lib.load(), C.c_void_p(_stream())
+            _lib.check(lib.cavp_optimizer_schedule(_ptr(self._sched), st), "cavp_optimizer_schedule")
+            _lib.check(lib.cavp_optimizer_step_dev(_ptr(self.table), self.njobs, self.total_blocks, C.c_float(self.momentum),
+                                                   C.c_float(self.eps), _ptr(self._sched), st), "cavp_optimizer_step_dev")
+            return
+        self._steps += 1
         b1, b2 = self.betas
         st = _lib.load().cavp_optimizer_step(_ptr(self.table), self.njobs, self.total_blocks, C.c_float(lr),
                                              C.c_float(self.base_lr), C.c_float(self.momentum), C.c_float(b1),
-                                             C.c_float(b2), C.c_float(self.eps), C.c_int64(self.steps),
+                                             C.c_float(b2), C.c_float(self.eps), C.c_int64(self._steps),
                                              C.c_void_p(_stream()))
         _lib.check(st, "cavp_optimizer_step")
 
     def state_dict(self) -> Dict[str, object]:
-        return {"steps": self.steps, "m": self.state_m.clone(), "v": self.state_v.clone()}
+        sd = {"steps": self.steps, "m": self.state_m.clone(), "v": self.state_v.clone()}
+        if self._sched is not None:
+            sd["t"] = sd["steps"]
+        return sd
 
     def load_state_dict(self, sd) -> None:
-        self.steps = int(sd["steps"])
+        self.steps = int(sd["t"]) if "t" in sd else int(sd["steps"])
         self.state_m.copy_(sd["m"])
         self.state_v.copy_(sd["v"])

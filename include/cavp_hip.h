@@ -437,6 +437,37 @@ int32_t cavp_optimizer_blocks(int64_t n);
 int cavp_optimizer_step(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float lr_sgd, float lr_adam,
                         float momentum, float beta1, float beta2, float eps, int64_t step, void* stream);
 
+/* Device-resident schedule (added to ABI 15): the step counter, the constants of the warm-up + poly schedule
+ * (engine/lr_policy.py:30-43) and of Adam, and the scalars of the current step, so that the optimiser step needs nothing
+ * from the host and can be recorded in a hipGraph.  The host fills t and the constants once; the device writes the rest.
+ * cavp_optimizer_schedule (one thread) computes, in double precision and rounded to f32 once, the scalars of step t:
+ *   lr_sgd = start_lr for t == 0, else get_lr(t - 1) (the reference sets the rate after the step), where get_lr(i) =
+ *            start_lr * i / warmup_steps for i < warmup_steps, end_lr for i >= total_iters (outside the reference's domain),
+ *            else clamp(start_lr * (1 - i / total_iters) ^ lr_power, end_lr, start_lr);
+ *   lr_adam = base_lr;  bc1 = 1 - beta1^(t+1);  bc2_sqrt = sqrt(1 - beta2^(t+1));  first_step = (t == 0);
+ * and then stores t + 1.  cavp_optimizer_step_dev is cavp_optimizer_step with those scalars loaded from the state block;
+ * issue it behind the schedule launch on the same stream.  Neither launch synchronises or touches host memory. */
+typedef struct cavp_opt_state {
+  int64_t t;            /* completed steps */
+  int64_t total_iters;
+  int64_t warmup_steps;
+  double start_lr;
+  double lr_power;
+  double end_lr;
+  float base_lr;        /* Adam's constant rate */
+  float beta1;
+  float beta2;
+  float lr_sgd;         /* from here on: written by the device */
+  float lr_adam;
+  float bc1;
+  float bc2_sqrt;
+  int32_t first_step;
+} cavp_opt_state;
+int64_t cavp_optimizer_state_bytes(void);
+int cavp_optimizer_schedule(cavp_opt_state* state_device, void* stream);
+int cavp_optimizer_step_dev(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum, float eps,
+                            const cavp_opt_state* state_device, void* stream);
+
 /* ---- log-mel front-end = trainers' preprocess_audio (trainer_cavp_vpo_mono.py:43-52,59-69;
  * utils/sourcesep.py:23-47): STFT(n_fft 512, hop, centred window, reflect padding) -> |.|^2 -> mel filterbank ->
  * 20 log10(max(amin, x)) -> 2 (x - spec_min) / (spec_max - spec_min) - 1.

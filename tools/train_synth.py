@@ -11,7 +11,7 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
-                                   [--contrast [--contrast-weight W]] [--pairs]
+                                   [--contrast [--contrast-weight W]] [--pairs] [--graph]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -19,6 +19,11 @@ ContrastLoss with the device sampler on the fusion map; the shuffle labels are t
 --pairs (with --from-waveform --contrast): the mismatched pairs are built as the reference trainers build them
 (trainer_cavp_vpo_mono.py:148-181), on the device: B clips and synthetic multi-hot image labels go through cavp_amd.pairs.PairBuilder
 (shuffle, overwrite from the sound bank from step 1 on, bank update), its 2B clips through MelFrontEnd, its label_shuffle into the step.
+
+--graph (with --from-waveform --contrast --pairs): the whole iteration as one hipGraph - pair builder, log-mel, forward, CE + contrast,
+backward and the optimiser step with the learning-rate schedule on the device (FusedSGDAdam.use_device_schedule,
+CAVP.capture_train_step(optimizer=, prologue=)).  Two captures share the optimiser's device state: one without the sound-bank
+overwrite for step 0, one with it for the rest.  The loop is "copy the batch into the static buffers, replay".
 """
 import argparse
 import os
@@ -53,9 +58,12 @@ def main():
     ap.add_argument("--max-views", type=int, default=512)
     ap.add_argument("--pairs", action="store_true", help="build the shuffled half of the batch and its labels with PairBuilder")
     ap.add_argument("--ow-rate", type=float, default=0.5, help="share of the mismatched rows overwritten from the sound bank")
+    ap.add_argument("--graph", action="store_true", help="one hipGraph per iteration: pairs, log-mel, step and optimiser (device schedule)")
     a = ap.parse_args()
     if a.pairs and not (a.from_waveform and a.contrast):
         ap.error("--pairs needs --from-waveform and --contrast")
+    if a.graph and not a.pairs:
+        ap.error("--graph needs --from-waveform --contrast --pairs")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -98,20 +106,74 @@ def main():
     opt = None
     t0 = None
     first = None
+
+    def draw_pairs_batch():
+        """B clips and synthetic multi-hot image labels (host tensors)"""
+        wave = torch.randn(B, 1, 16000, generator=g) * 0.1
+        img_label = torch.zeros(B, pairs.K, dtype=torch.int64)
+        img_label[torch.arange(B), torch.randint(1, pairs.K, (B,), generator=g)] = 1       # one source per frame ...
+        two = torch.rand(B, generator=g) < 0.25                                             # ... a second one for a quarter
+        img_label[two, torch.randint(1, pairs.K, (int(two.sum()),), generator=g)] = 1
+        img_label[:, 0] = torch.randint(0, 2, (B,), generator=g)
+        return wave, img_label
+
+    replays = None
+    if a.graph:
+        from cavp_amd.pairs import PairResult
+        s_image = torch.zeros(B, 3, a.hw, a.hw, device=dev)
+        s_label = torch.zeros(B, a.hw, a.hw, dtype=torch.int64, device=dev)
+        s_wave = torch.zeros(B, 1, 16000, device=dev)
+        s_img_label = torch.zeros(B, pairs.K, dtype=torch.int64, device=dev)
+        s_img_label[:, 1] = 1
+        s_audio = torch.zeros(2 * B, 1, front.n_frames, front.n_mels, device=dev)
+        s_shuf = torch.zeros_like(s_label)
+        built = PairResult(B, 16000, pairs.K, (a.hw, a.hw), dev)
+        opt = FusedSGDAdam(model, model.grad_arena(dev), a.lr, momentum=a.momentum, weight_decay=a.weight_decay)
+        opt.use_device_schedule(a.lr, a.lr_power, a.total_iters, 0)
+        start = {k: v.clone() for k, v in model.state_dict().items()}
+
+        def prologue_of(overwrite):
+            def prologue():
+                pairs(s_wave, s_label, s_img_label, overwrite, out=built)
+                s_audio.copy_(front(built.waveforms))
+                s_shuf.copy_(built.label_shuffle)
+            return prologue
+        replays = []
+        for ow in (False, True):
+            rep = model.capture_train_step(s_image, s_audio, s_label, contrast=crit, label_shuffle=s_shuf,
+                                           contrast_weight=a.contrast_weight, optimizer=opt, prologue=prologue_of(ow))
+            replays.append((rep, model._last_losses))           # (each graph has its own static loss buffers)
+        # the warm-up passes of the captures ran the pair builder, the sampler and the BatchNorm statistics for real: start over
+        model.load_state_dict(start)
+        pairs.manual_seed(1234 + rank)
+        pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
+        crit.manual_seed(1234 + rank)
+
     for it in range(a.steps):
         if a.fixed_batch:
             g = torch.Generator().manual_seed(1234 + rank)      # the same batch every step
-        image = torch.randn(B, 3, a.hw, a.hw, generator=g).to(dev)
-        label = torch.randint(0, a.num_classes, (B, a.hw, a.hw), generator=g).to(dev)
+        image = torch.randn(B, 3, a.hw, a.hw, generator=g)
+        label = torch.randint(0, a.num_classes, (B, a.hw, a.hw), generator=g)
+        if replays is not None:                                 # copy the batch in, replay: nothing else is launched from here
+            wave, img_label = draw_pairs_batch()
+            for dst, src in ((s_image, image), (s_label, label), (s_wave, wave), (s_img_label, img_label)):
+                dst.copy_(src)
+            rep, graph_terms = replays[1 if it >= 1 else 0]
+            loss = rep()
+            if it == 1:
+                torch.cuda.synchronize()
+                t0 = time.time()
+            if first is None:
+                first = float(loss.item())
+            if rank == 0 and (it % 5 == 0 or it == a.steps - 1):
+                terms = "  (CE {:.4f}, contrast {:.4f})".format(*(float(t.item()) for t in graph_terms))
+                print(f"iter {it:4d}  lr {float(opt.last_lr().item()):.3e}  loss {float(loss.item()):.4f}{terms}", flush=True)
+            continue
+        image, label = image.to(dev), label.to(dev)
         built = None
         if pairs is not None:                                   # B clips + image labels -> matched ‖ shuffled clips, shuffle labels
-            wave = (torch.randn(B, 1, 16000, generator=g) * 0.1).to(dev)
-            img_label = torch.zeros(B, pairs.K, dtype=torch.int64)
-            img_label[torch.arange(B), torch.randint(1, pairs.K, (B,), generator=g)] = 1       # one source per frame ...
-            two = torch.rand(B, generator=g) < 0.25                                             # ... a second one for a quarter
-            img_label[two, torch.randint(1, pairs.K, (int(two.sum()),), generator=g)] = 1
-            img_label[:, 0] = torch.randint(0, 2, (B,), generator=g)
-            built = pairs(wave, label, img_label.to(dev), overwrite=it >= 1)
+            wave, img_label = draw_pairs_batch()
+            built = pairs(wave.to(dev), label, img_label.to(dev), overwrite=it >= 1)
             audio = front(built.waveforms)
         elif front is not None:                                 # matched clips ‖ shuffled clips = 2B (cavp_model.py:181)
             wave = (torch.randn(2 * B, 1, 16000, generator=g) * 0.1).to(dev)
@@ -144,7 +206,7 @@ def main():
     if rank == 0 and t0 is not None and a.steps > 2:
         dt = (time.time() - t0) / (a.steps - 2)
         print(f"{B * world / dt:.1f} frames/s over {world} GPU(s) ({dt * 1e3:.1f} ms/step incl. host-side input generation, "
-              f"eager launches, optimiser step)")
+              f"{'one graph replay' if a.graph else 'eager launches, optimiser step'})")
     if rank == 0 and pairs is not None:
         plan = pairs.last_plan()
         print(f"pairs, last step: {int(plan['if_match'].sum())} of {B} rows matched, {plan['n_overwritten']} taken from the sound bank "
