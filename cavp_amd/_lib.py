@@ -173,6 +173,10 @@ PROTOTYPES = {
     "cavp_pairs_gather": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "cavp_pairs_bank_update": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "cavp_pairs_labels": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    # ---- frame augmentation: flip, scale, jitter, pad, crop (added to ABI 15) ----
+    "cavp_aug_plan": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_aug_contrast_mean": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "cavp_aug_render": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

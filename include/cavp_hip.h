@@ -686,6 +686,43 @@ int cavp_pairs_bank_update(const float* waveform, const int32_t* wr_table, int32
                            void* stream);
 int cavp_pairs_labels(const int64_t* pix_label, const uint8_t* if_match, int32_t B, int64_t HW, int64_t* label_shuffle, void* stream);
 
+/* ---- Frame augmentation (three entry points added to ABI 15; nothing else changed): VisualAugmentation.train_aug of the reference
+ * (dataset/<set>/visual/visual_aug.py) on raw decoded uint8 frames, PIL's arithmetic restated (tests/_augment_ref.py) ----
+ * frames uint8 [B][Hs][Ws][3] and masks uint8 [B][Hs][Ws]: sample i sits in the top-left h x w corner of its staging slot,
+ * (h, w) = sizes int32 [B][2] on the device; bytes outside the corner are never read.  Launch order on one stream: plan,
+ * contrast_mean (only with jitter), render.  B <= 1024, crop H <= Hs, W <= Ws.
+ *
+ * params int32 [B][16], one row per sample (written by plan; params_in, optional, has the same layout and replaces the draws,
+ * words 12 .. 15 of it are ignored):
+ *   0 flip   1 scale index   2..5 order of the jitter operations (a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue)
+ *   6, 7, 8 brightness / contrast / saturation factor (f32 bits)   9 hue shift, the uint8 added to H   10 crop top   11 crop left
+ *   12, 13 scaled height / width   14 the contrast degenerate (rounded mean of L; written by render, -1 without jitter)
+ *   15 non-zero: this sample was counted in bad_inputs
+ * cavp_aug_plan (one workgroup): draws with Philox4x32-10, counter = (sample, stream, offset_lo, offset_hi), key = seed (the
+ *   device sampler's convention); stream 0: r0 -> flip = u > 0.5, r1 -> scale index; 1: r0 -> one of the 24 orders, r1 ->
+ *   brightness = 0.5 + u; 2: contrast, saturation; 3: r0 -> hue = -0.25 + 0.5 u, shift = trunc(hue * 255) mod 256; 4: top, left
+ *   (u = (r >> 8) / 2^24; an index below n = (r * n) >> 32).  scales64: HOST int32 [n_scales], scale = value / 64, 32 <= value
+ *   <= 256, n_scales <= 16.  Scaled size = floor(h * value / 64) (the reference's int(h * s), exact).  Pad as the reference
+ *   writes it: if min(sh, sw) < min(H, W): right = max(H - sw, 0), bottom = max(W - sh, 0); top in [0, ph - H], left in [0, pw - W].
+ *   identity != 0: the test-time path (no draw, scale 1, window at the origin).  state int64[4] (device): {seed, offset,
+ *   bad_inputs, reserved}; a call reads seed / offset, then offset += 1 and bad_inputs += the samples with a staged size outside
+ *   1 <= h <= Hs, 1 <= w <= Ws, an empty scaled image, a params_in field out of range or a padded image that cannot hold the
+ *   crop; those are rendered from clamped values, nothing is read or written out of bounds.  near_tab int32 [B][H + W]: PIL's
+ *   NEAREST source row / column (mirrored under flip) of every crop row / column, -1 in the pad.  lsum uint64 [B]: zeroed.
+ * cavp_aug_contrast_mean: lsum[i] += sum of L over the whole scaled image of sample i after the operations in front of the
+ *   contrast one (exact integer atomics: bit-reproducible).  max_scale64 = the largest entry of scales64 (sizes the grid).
+ * cavp_aug_render: image f32 [B][3][H][W] = ((u8 / 255) - mean) / std, label int64 [B][H][W]; one 16 x 64 tile of the crop per
+ *   workgroup, the horizontally resampled rows in LDS.  mean3 / std3 (f32) and fill3 (int32, 0 .. 255) are HOST arrays of 3.
+ * No allocation, no synchronisation, no host read of a device value: the launches are capturable in a hipGraph. */
+int cavp_aug_plan(const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* scales64,
+                  int32_t n_scales, int32_t jitter, int32_t identity, const int32_t* params_in, int64_t* state, int32_t* params,
+                  int32_t* near_tab, uint64_t* lsum, void* stream);
+int cavp_aug_contrast_mean(const uint8_t* frames, const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t max_scale64,
+                           const int32_t* params, uint64_t* lsum, void* stream);
+int cavp_aug_render(const uint8_t* frames, const uint8_t* masks, const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H,
+                    int32_t W, const float* mean3, const float* std3, const int32_t* fill3, int32_t jitter, int32_t* params,
+                    const int32_t* near_tab, const uint64_t* lsum, float* image, int64_t* label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
