@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(HERE, "libcavp_hip.so")
 
 F32, BF16, I64 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_GELU = 0, 1, 2, 3
-ABI_VERSION = 15
+ABI_VERSION = 16
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_WORKSPACE, ERR_LAUNCH = -1, -2, -3, -4, -5   # cavp_status_t
 WGRAD_GROUP_MAX = 16   # CAVP_WGRAD_GROUP_MAX
 
@@ -129,19 +129,15 @@ PROTOTYPES = {
                               _vp, _vp, _vp]),
     # ---- contrastive loss ----
     "cavp_label_nearest": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "cavp_gather_l2norm": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
-    "cavp_infonce_rows": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _f32, _vp]),
-    "cavp_symm_add": (_i32, [_vp, _vp, _i32, _f32, _vp]),
-    "cavp_symm_add_scaled": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
-    "cavp_l2norm_bwd_scatter": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _vp]),
+    "cavp_gather_l2norm": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp,
+                                  _vp, _vp]),
+    "cavp_infonce_rows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _f32, _vp]),
+    "cavp_symm_add": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
+    "cavp_l2norm_bwd_scatter": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
+                                       _i64, _vp]),
     # ---- contrastive loss, device-side sampling (ABI 14) ----
     "cavp_contrast_sample_work_bytes": (_sz, [_i32]),
     "cavp_contrast_sample": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cavp_gather_l2norm_dev": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp,
-                                      _vp]),
-    "cavp_infonce_rows_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _f32, _vp]),
-    "cavp_l2norm_bwd_scatter_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64,
-                                           _vp]),
     # ---- contrastive loss on the training tape's [2B][HW][ld] compute-dtype fusion map ----
     "cavp_contrast_gather_nhwc": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "cavp_contrast_rows_bwd_add": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32,

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -182,60 +182,6 @@ def _strides_bcp(x: torch.Tensor) -> Tuple[int, int, int]:
     return sb, sc, sw
 
 
-class _InfoNCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, em, es, plan: SamplePlan, temperature: float, eps: float):
-        lib = _lib.load()
-        dev = em.device
-        st = C.c_void_p(_stream())
-        Cc = em.shape[1]
-        n, npad = plan.n, (plan.n + 3) // 4 * 4
-        ib, ip, lab = _upload_i32((plan.b, plan.p, plan.labels), dev)
-        A = torch.zeros((npad, Cc), dtype=torch.float32, device=dev)
-        norms = torch.empty(npad, dtype=torch.float32, device=dev)
-        for x, lo, hi in ((em, 0, plan.n_match), (es, plan.n_match, n)):
-            if hi > lo:
-                sb, sc, sp = _strides_bcp(x)
-                _lib.check(lib.cavp_gather_l2norm(_ptr(x), sb, sc, sp, _ptr(ib[lo:]), _ptr(ip[lo:]), hi - lo, Cc,
-                                                  C.c_float(1e-12), _ptr(A[lo:]), _ptr(norms[lo:]), st), "cavp_gather_l2norm")
-        S = torch.empty((npad, npad), dtype=torch.float32, device=dev)
-        inv_t = torch.full((npad,), 1.0 / temperature, dtype=torch.float32, device=dev)
-        ops.linear(A, A.view(npad, 1, 1, Cc), S, scale=inv_t)          # S = A A^T / T on the f32 MFMA path
-        rows = torch.empty(npad, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        need_grad = em.requires_grad or es.requires_grad
-        dS = torch.empty_like(S) if need_grad else None
-        _lib.check(lib.cavp_infonce_rows(_ptr(S), _ptr(lab), n, npad, C.c_float(eps), _ptr(rows), _ptr(loss), _ptr(dS),
-                                         C.c_float(1.0), st), "cavp_infonce_rows")
-        ctx.saved = (A, norms, dS, ib, ip, plan, em, es, temperature)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = _lib.load()
-        A, norms, dS, ib, ip, plan, em, es, temperature = ctx.saved
-        st = C.c_void_p(_stream())
-        npad, Cc = A.shape
-        n = plan.n
-        G = torch.empty_like(dS)
-        # dL/dA = (dS + dS^T) A / T  (anchors and contrasts are the same tensor), scaled by the incoming gradient
-        # (the upstream gradient is a device scalar: it is multiplied in on the device - float(gout) made the host wait for the
-        # whole forward + loss queue before it could launch the backward)
-        gs = gout.detach().reshape(1).to(torch.float32)
-        _lib.check(lib.cavp_symm_add_scaled(_ptr(dS), _ptr(G), npad, C.c_float(1.0 / temperature), _ptr(gs), st), "cavp_symm_add_scaled")
-        dA = torch.zeros((npad, Cc), dtype=torch.float32, device=A.device)
-        T.linear_wgrad(A, G, dA)
-        grads = []
-        for x, lo, hi in ((em, 0, plan.n_match), (es, plan.n_match, n)):
-            b, c, h, w = x.shape
-            g = torch.zeros((b, h, w, c), dtype=torch.float32, device=x.device)   # NHWC memory, returned as an NCHW view
-            if hi > lo:
-                _lib.check(lib.cavp_l2norm_bwd_scatter(_ptr(dA[lo:]), _ptr(A[lo:]), _ptr(norms[lo:]), _ptr(ib[lo:]), _ptr(ip[lo:]),
-                                                       hi - lo, Cc, _ptr(g), h * w * c, 1, c, st), "cavp_l2norm_bwd_scatter")
-            grads.append(g.permute(0, 3, 1, 2))
-        return grads[0], grads[1], None, None, None
-
-
 class DevicePlan:
     """What the device sampler chose in one call; every field is a device tensor.  header: int32[8] = {n, n_match, k_kept,
     sample_num, offset_lo, offset_hi, seed_lo, seed_hi}; idx_b / idx_p / labels: int32[cap] (rows >= n hold -1)."""
@@ -264,54 +210,89 @@ def sample_anchors_device(gm: torch.Tensor, gs: torch.Tensor, ignore_idx: int, m
     return DevicePlan(header, ib, ip, lab, cap, work, gm, gs)
 
 
-class _InfoNCEDeviceFn(torch.autograd.Function):
-    """_InfoNCEFn with the anchor count on the device: every buffer has the static capacity of the plan, the kernels read n and
-    n_match from the plan header.  No host decision depends on a device value, in either direction."""
+class _PlanArgs(NamedTuple):
+    """What a launch of the chain needs, for either plan type.  header None: the count is the host's (n, n_match), cap 0; else the
+    count is read from the header on the device and n = n_match = 0.  npad: the row count of A / S."""
+    header: Optional[torch.Tensor]
+    idx_b: torch.Tensor
+    idx_p: torch.Tensor
+    labels: Optional[torch.Tensor]
+    cap: int
+    n: int
+    n_match: int
+    npad: int
+
+
+def _plan_args(plan, dev=None, idx=None) -> _PlanArgs:
+    """A SamplePlan's three arrays are uploaded to `dev` here (once per step: the chain keeps the result).  A caller that holds the
+    index arrays on the device already passes idx = (idx_b, idx_p) and gets no labels."""
+    if isinstance(plan, DevicePlan):
+        return _PlanArgs(plan.header, plan.idx_b, plan.idx_p, plan.labels, plan.cap, 0, 0, (plan.cap + 3) // 4 * 4)
+    if idx is not None:
+        ib, ip, lab = idx[0], idx[1], None
+    elif dev is not None:
+        ib, ip, lab = _upload_i32((plan.b, plan.p, plan.labels), dev)
+    else:
+        raise _lib.CavpError("a SamplePlan needs its index arrays on the device: idx = (idx_b, idx_p)")
+    return _PlanArgs(None, ib, ip, lab, 0, plan.n, plan.n_match, (plan.n + 3) // 4 * 4)
+
+
+def _infonce_from_rows(A: torch.Tensor, pa: _PlanArgs, temperature: float, eps: float, need_grad: bool = True):
+    """The middle of the chain on the filled A [npad, C]: S = A A^T / T on the f32 MFMA path, the InfoNCE rows, loss (f32 [1]) and,
+    with need_grad, dS = dloss / dS.  Returns (S, rows, loss, dS)."""
+    dev, (npad, Cc) = A.device, A.shape
+    S = torch.empty((npad, npad), dtype=torch.float32, device=dev)
+    inv_t = torch.full((npad,), 1.0 / temperature, dtype=torch.float32, device=dev)
+    ops.linear(A, A.view(npad, 1, 1, Cc), S, scale=inv_t)
+    rows = torch.empty(npad, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dS = torch.empty_like(S) if need_grad else None
+    _lib.check(_lib.load().cavp_infonce_rows(_ptr(S), _ptr(pa.labels), _ptr(pa.header), pa.cap, pa.n, npad, C.c_float(eps), _ptr(rows),
+                                             _ptr(loss), _ptr(dS), C.c_float(1.0), C.c_void_p(_stream())), "cavp_infonce_rows")
+    return S, rows, loss, dS
+
+
+def _rows_grad(dS: torch.Tensor, A: torch.Tensor, scale: float, scale_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dL/dA = scale * scale_dev[0] * (dS + dS^T) A  (anchors and contrasts are the same tensor: both roles get gradient).  scale_dev is
+    a device scalar, multiplied in on the device - float(gout) made the host wait for the whole forward + loss queue before it
+    could launch the backward."""
+    G = torch.empty_like(dS)
+    _lib.check(_lib.load().cavp_symm_add(_ptr(dS), _ptr(G), dS.shape[0], C.c_float(scale), _ptr(scale_dev), C.c_void_p(_stream())),
+               "cavp_symm_add")
+    dA = T.zeros(tuple(A.shape), torch.float32, A.device)
+    T.linear_wgrad(A, G, dA)
+    return dA
+
+
+class _InfoNCEFn(torch.autograd.Function):
+    """The loss on the f32 feature maps [B, C, h, w] (any uniform pixel stride) for a SamplePlan or a DevicePlan.  With a DevicePlan
+    every buffer has the static capacity of the plan and the kernels read n and n_match from the plan header: no host decision
+    depends on a device value, in either direction."""
 
     @staticmethod
-    def forward(ctx, em, es, plan: DevicePlan, temperature: float, eps: float):
-        lib = _lib.load()
-        dev = em.device
-        st = C.c_void_p(_stream())
+    def forward(ctx, em, es, plan, temperature: float, eps: float):
+        pa = _plan_args(plan, em.device)
         Cc = em.shape[1]
-        cap, npad = plan.cap, (plan.cap + 3) // 4 * 4
-        A = torch.empty((npad, Cc), dtype=torch.float32, device=dev)
-        norms = torch.empty(npad, dtype=torch.float32, device=dev)
-        _lib.check(lib.cavp_gather_l2norm_dev(_ptr(em), *_strides_bcp(em), _ptr(es), *_strides_bcp(es), _ptr(plan.header),
-                                              _ptr(plan.idx_b), _ptr(plan.idx_p), cap, npad, Cc, C.c_float(1e-12), _ptr(A),
-                                              _ptr(norms), st), "cavp_gather_l2norm_dev")
-        S = torch.empty((npad, npad), dtype=torch.float32, device=dev)
-        inv_t = torch.full((npad,), 1.0 / temperature, dtype=torch.float32, device=dev)
-        ops.linear(A, A.view(npad, 1, 1, Cc), S, scale=inv_t)          # S = A A^T / T at the static capacity
-        rows = torch.empty(npad, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        need_grad = em.requires_grad or es.requires_grad
-        dS = torch.empty_like(S) if need_grad else None
-        _lib.check(lib.cavp_infonce_rows_dev(_ptr(S), _ptr(plan.labels), _ptr(plan.header), cap, npad, C.c_float(eps), _ptr(rows),
-                                             _ptr(loss), _ptr(dS), C.c_float(1.0), st), "cavp_infonce_rows_dev")
-        ctx.saved = (A, norms, dS, plan, em, es, temperature)
+        A = torch.empty((pa.npad, Cc), dtype=torch.float32, device=em.device)    # the kernel writes the padding rows
+        norms = torch.empty(pa.npad, dtype=torch.float32, device=em.device)
+        _lib.check(_lib.load().cavp_gather_l2norm(_ptr(em), *_strides_bcp(em), _ptr(es), *_strides_bcp(es), _ptr(pa.header),
+                                                  _ptr(pa.idx_b), _ptr(pa.idx_p), pa.cap, pa.n, pa.n_match, pa.npad, Cc,
+                                                  C.c_float(1e-12), _ptr(A), _ptr(norms), C.c_void_p(_stream())), "cavp_gather_l2norm")
+        _, _, loss, dS = _infonce_from_rows(A, pa, temperature, eps, em.requires_grad or es.requires_grad)
+        ctx.saved = (A, norms, dS, pa, em.shape, es.shape, temperature)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load()
-        A, norms, dS, plan, em, es, temperature = ctx.saved
-        st = C.c_void_p(_stream())
-        npad, Cc = A.shape
-        G = torch.empty_like(dS)
-        gs = gout.detach().reshape(1).to(torch.float32)
-        _lib.check(lib.cavp_symm_add_scaled(_ptr(dS), _ptr(G), npad, C.c_float(1.0 / temperature), _ptr(gs), st), "cavp_symm_add_scaled")
-        dA = T.zeros((npad, Cc), torch.float32, A.device)
-        T.linear_wgrad(A, G, dA)
-        grads = []
-        for x in (em, es):
-            b, c, h, w = x.shape
-            grads.append(T.zeros((b, h, w, c), torch.float32, x.device))   # NHWC memory, cleared by a launch; NCHW views returned
-        (_, _, h, w), c = em.shape, Cc
-        _lib.check(lib.cavp_l2norm_bwd_scatter_dev(_ptr(dA), _ptr(A), _ptr(norms), _ptr(plan.header), _ptr(plan.idx_b),
-                                                   _ptr(plan.idx_p), plan.cap, Cc, _ptr(grads[0]), h * w * c, 1, c, _ptr(grads[1]),
-                                                   h * w * c, 1, c, st), "cavp_l2norm_bwd_scatter_dev")
-        return grads[0].permute(0, 3, 1, 2), grads[1].permute(0, 3, 1, 2), None, None, None
+        A, norms, dS, pa, em_shape, es_shape, temperature = ctx.saved
+        dA = _rows_grad(dS, A, 1.0 / temperature, gout.detach().reshape(1).to(torch.float32))
+        # NHWC memory, cleared by a launch; NCHW views are returned
+        gm, gs = (T.zeros((b, h, w, c), torch.float32, A.device) for b, c, h, w in (em_shape, es_shape))
+        _lib.check(_lib.load().cavp_l2norm_bwd_scatter(_ptr(dA), _ptr(A), _ptr(norms), _ptr(pa.header), _ptr(pa.idx_b), _ptr(pa.idx_p),
+                                                       pa.cap, pa.n, pa.n_match, A.shape[1], _ptr(gm), *_strides_bcp(gm.permute(0, 3, 1, 2)), _ptr(gs),
+                                                       *_strides_bcp(gs.permute(0, 3, 1, 2)), C.c_void_p(_stream())),
+                   "cavp_l2norm_bwd_scatter")
+        return gm.permute(0, 3, 1, 2), gs.permute(0, 3, 1, 2), None, None, None
 
 
 class ContrastLoss(nn.Module):
@@ -396,7 +377,7 @@ class ContrastLoss(nn.Module):
         plan = sample_anchors_device(_label_nearest_device(gt_match, (h, w)), _label_nearest_device(gt_shuffle, (h, w)),
                                      self.ignore_idx, self.max_views, max_classes, state)
         self._last_plan = plan
-        return _InfoNCEDeviceFn.apply(em, es, plan, float(self.temperature), float(self.eps))
+        return _InfoNCEFn.apply(em, es, plan, float(self.temperature), float(self.eps))
 
     @staticmethod
     def prefetch_labels(gt_match, gt_shuffle, size) -> None:
@@ -452,20 +433,14 @@ def _nhwc_map_args(x: torch.Tensor, what: str):
     return n2 // 2, hw, ld, Cc
 
 
-def _plan_args(plan, idx):
-    """(header, idx_b, idx_p, cap, N, n_match) of a DevicePlan, or of a SamplePlan whose index arrays `idx` are on the device."""
-    if isinstance(plan, DevicePlan):
-        return _ptr(plan.header), _ptr(plan.idx_b), _ptr(plan.idx_p), plan.cap, 0, 0
-    return None, _ptr(idx[0]), _ptr(idx[1]), 0, plan.n, plan.n_match
-
-
 def contrast_gather_nhwc(x: torch.Tensor, plan, idx, A: torch.Tensor, norms: torch.Tensor, eps: float = 1e-12) -> None:
     """A[i] = x_row / max(||x_row||, eps) (f32 [rows, C]) and norms[i] for the plan's anchors, read from the map in its own dtype."""
     B, hw, ld, Cc = _nhwc_map_args(x, "contrast_gather_nhwc")
     if A.dtype != torch.float32 or norms.dtype != torch.float32 or not A.is_contiguous() or A.shape[1] != Cc or norms.numel() < A.shape[0]:
         raise _lib.CavpError("contrast_gather_nhwc: A must be dense f32 [rows, C] with one norm per row")
-    header, ib, ip, cap, n, nm = _plan_args(plan, idx)
-    _lib.check(_lib.load().cavp_contrast_gather_nhwc(ops.dtype_code(x.dtype), _ptr(x), B, hw, ld, Cc, header, ib, ip, cap, n, nm,
+    pa = _plan_args(plan, idx=idx)
+    _lib.check(_lib.load().cavp_contrast_gather_nhwc(ops.dtype_code(x.dtype), _ptr(x), B, hw, ld, Cc, _ptr(pa.header), _ptr(pa.idx_b),
+                                                     _ptr(pa.idx_p), pa.cap, pa.n, pa.n_match,
                                                      A.shape[0], C.c_float(eps), _ptr(A), _ptr(norms), C.c_void_p(_stream())),
                "cavp_contrast_gather_nhwc")
 
@@ -476,10 +451,11 @@ def contrast_rows_bwd_add(g: torch.Tensor, plan, idx, dA: torch.Tensor, A: torch
     for t in (dA, A):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != Cc:
             raise _lib.CavpError("contrast_rows_bwd_add: A / dA must be dense f32 [rows, C]")
-    header, ib, ip, cap, n, nm = _plan_args(plan, idx)
-    if min(A.shape[0], dA.shape[0], norms.numel()) < (cap if header is not None else n):
+    pa = _plan_args(plan, idx=idx)
+    if min(A.shape[0], dA.shape[0], norms.numel()) < (pa.cap if pa.header is not None else pa.n):
         raise _lib.CavpError("contrast_rows_bwd_add: A / dA / norms hold fewer rows than the plan")
-    _lib.check(_lib.load().cavp_contrast_rows_bwd_add(ops.dtype_code(g.dtype), _ptr(g), B, hw, ld, Cc, header, ib, ip, cap, n, nm,
+    _lib.check(_lib.load().cavp_contrast_rows_bwd_add(ops.dtype_code(g.dtype), _ptr(g), B, hw, ld, Cc, _ptr(pa.header), _ptr(pa.idx_b),
+                                                      _ptr(pa.idx_p), pa.cap, pa.n, pa.n_match,
                                                       _ptr(dA), _ptr(A), _ptr(norms), C.c_float(scale), C.c_void_p(_stream())),
                "cavp_contrast_rows_bwd_add")
 
@@ -520,41 +496,19 @@ class NativeContrastTerm:
 
     def run(self, fusion: torch.Tensor, grad_scale: float) -> torch.Tensor:
         """fusion: the tape's map [2B, h, w, C].  grad_scale: d(total loss) / d(this term).  Leaves what add_rows needs."""
-        lib, dev, st = _lib.load(), fusion.device, C.c_void_p(_stream())
+        dev = fusion.device
         if tuple(fusion.shape[1:3]) != self.size:
             raise _lib.CavpError(f"train_step(contrast=...): the fusion map is {tuple(fusion.shape[1:3])}, the labels were reduced to {self.size}")
         plan = self.plan
         if plan is None:
             return T.zeros((1,), torch.float32, dev)
-        Cc = fusion.shape[-1]
-        idx = lab = None
-        if isinstance(plan, DevicePlan):
-            npad = (plan.cap + 3) // 4 * 4
-        else:
-            npad = (plan.n + 3) // 4 * 4
-            ib, ip, lab = _upload_i32((plan.b, plan.p, plan.labels), dev)
-            idx = (ib, ip)
-        A = torch.empty((npad, Cc), dtype=torch.float32, device=dev)
-        norms = torch.empty(npad, dtype=torch.float32, device=dev)
+        pa = _plan_args(plan, dev)
+        idx = (pa.idx_b, pa.idx_p)
+        A = torch.empty((pa.npad, fusion.shape[-1]), dtype=torch.float32, device=dev)
+        norms = torch.empty(pa.npad, dtype=torch.float32, device=dev)
         contrast_gather_nhwc(fusion, plan, idx, A, norms)
-        S = torch.empty((npad, npad), dtype=torch.float32, device=dev)
-        inv_t = torch.full((npad,), 1.0 / self.crit.temperature, dtype=torch.float32, device=dev)
-        ops.linear(A, A.view(npad, 1, 1, Cc), S, scale=inv_t)
-        rows = torch.empty(npad, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        dS = torch.empty_like(S)
-        eps = C.c_float(float(self.crit.eps))
-        if isinstance(plan, DevicePlan):
-            _lib.check(lib.cavp_infonce_rows_dev(_ptr(S), _ptr(plan.labels), _ptr(plan.header), plan.cap, npad, eps, _ptr(rows),
-                                                 _ptr(loss), _ptr(dS), C.c_float(1.0), st), "cavp_infonce_rows_dev")
-        else:
-            _lib.check(lib.cavp_infonce_rows(_ptr(S), _ptr(lab), plan.n, npad, eps, _ptr(rows), _ptr(loss), _ptr(dS), C.c_float(1.0), st),
-                       "cavp_infonce_rows")
-        G = torch.empty_like(dS)
-        # dL/dA = grad_scale * (dS + dS^T) A / T  (anchors and contrasts are the same tensor)
-        _lib.check(lib.cavp_symm_add(_ptr(dS), _ptr(G), npad, C.c_float(grad_scale / self.crit.temperature), st), "cavp_symm_add")
-        dA = T.zeros((npad, Cc), torch.float32, dev)
-        T.linear_wgrad(A, G, dA)
+        _, _, loss, dS = _infonce_from_rows(A, pa, self.crit.temperature, float(self.crit.eps))
+        dA = _rows_grad(dS, A, grad_scale / self.crit.temperature)
         self.saved = (plan, idx, dA, A, norms)
         return loss
 

@@ -2,7 +2,8 @@
 // the normalise / gather part of ::forward / ::extraction_samples).  By default the class-balanced SAMPLING stays on the host
 // (it consumes torch.randperm from the CPU generator; reproducing the reference's indices needs the same RNG stream);
 // the host hands over (image, pixel) index lists + labels of the N <= ~3000 anchors.  The opt-in device sampler (second half
-// of this file) picks the anchors here, with Philox keys, and the *_dev entry points read the anchor count from its plan.
+// of this file) picks the anchors here, with Philox keys.  Every kernel of the chain takes its anchor count from anchor_count():
+// the sampler's plan header on the device, or the host's (N, n_match) when there is no header.
 //   1. gather_l2norm:   A[i] = x[b_i, :, p_i] / max(||.||_2, eps)         (F.normalize(dim=1) then boolean gather)
 //   2. S = A A^T / T:   the f32 MFMA igemm (cavp_conv2d_nhwc, weights = A)
 //   3. infonce_rows:    one workgroup per anchor row: max, negative sum, per-positive log-prob, mean; optional dS
@@ -31,14 +32,33 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// one wave per anchor
-__global__ __launch_bounds__(256) void gather_l2norm_kernel(const float* __restrict__ x, long long sb, long long sc,
-                                                            long long sp, const int* __restrict__ ib,
-                                                            const int* __restrict__ ip, int N, int C, float eps,
-                                                            float* __restrict__ A, float* __restrict__ norms) {
+// The anchor count of a launch: from the device sampler's plan header (cap = the plan's capacity; N / n_match ignored) or,
+// header == nullptr, from the host.  Rows < n_match belong to the match half, the others to the shuffle half.
+struct AnchorCount { int n, n_match; };
+__device__ __forceinline__ AnchorCount anchor_count(const int* __restrict__ header, int cap, int N, int n_match) {
+  if (!header) return {N, n_match};
+  int n = header[0];
+  n = n < 0 ? 0 : (n > cap ? cap : n);
+  return {n, header[1]};
+}
+
+// one wave per row of A; rows >= n are zero (norm 1)
+__global__ __launch_bounds__(256) void gather_l2norm_kernel(const float* __restrict__ xm, long long msb, long long msc, long long msp,
+                                                            const float* __restrict__ xs, long long ssb, long long ssc, long long ssp,
+                                                            const int* __restrict__ header, const int* __restrict__ ib,
+                                                            const int* __restrict__ ip, int cap, int N, int n_match, int rows, int C,
+                                                            float eps, float* __restrict__ A, float* __restrict__ norms) {
   const int lane = threadIdx.x & 63;
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < N; i += gridDim.x * 4) {
-    const float* src = x + (long long)ib[i] * sb + (long long)ip[i] * sp;
+  const AnchorCount cnt = anchor_count(header, cap, N, n_match);
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < rows; i += gridDim.x * 4) {
+    if (i >= cnt.n) {
+      for (int c = lane; c < C; c += 64) A[(size_t)i * C + c] = 0.f;
+      if (lane == 0) norms[i] = 1.f;
+      continue;
+    }
+    const bool m = i < cnt.n_match;
+    const long long sc = m ? msc : ssc;
+    const float* src = m ? xm + (long long)ib[i] * msb + (long long)ip[i] * msp : xs + (long long)ib[i] * ssb + (long long)ip[i] * ssp;
     float q = 0.f;
     for (int c = lane; c < C; c += 64) { const float v = src[(long long)c * sc]; q += v * v; }
     const float nrm = fmaxf(sqrtf(wave_sum(q)), eps);
@@ -97,19 +117,21 @@ __device__ __forceinline__ void infonce_row(const float* __restrict__ S, const i
   }
 }
 
-__global__ __launch_bounds__(256) void infonce_rows_kernel(const float* __restrict__ S, const int* __restrict__ lab, int N,
-                                                           int ld, float eps, float* __restrict__ out_rows,
-                                                           float* __restrict__ dS, float grad_scale) {
+__global__ __launch_bounds__(256) void infonce_rows_kernel(const float* __restrict__ S, const int* __restrict__ lab,
+                                                           const int* __restrict__ header, int cap, int N, int ld, float eps,
+                                                           float* __restrict__ out_rows, float* __restrict__ dS, float grad_scale) {
   __shared__ float red[4];
-  infonce_row(S, lab, N, ld, eps, out_rows, dS, grad_scale, red);
+  infonce_row(S, lab, anchor_count(header, cap, N, 0).n, ld, eps, out_rows, dS, grad_scale, red);
 }
 
-__global__ __launch_bounds__(256) void mean_neg_kernel(const float* rows, int N, float* loss) {
+// loss = -mean(rows[0 .. n)); 0 when the plan is empty
+__global__ __launch_bounds__(256) void mean_neg_kernel(const float* rows, const int* __restrict__ header, int cap, int N, float* loss) {
   __shared__ float red[4];
+  const int n = anchor_count(header, cap, N, 0).n;
   float s = 0.f;
-  for (int j = threadIdx.x; j < N; j += 256) s += rows[j];
+  for (int j = threadIdx.x; j < n; j += 256) s += rows[j];
   s = block_sum(s, red);
-  if (threadIdx.x == 0) loss[0] = -s / (float)N;
+  if (threadIdx.x == 0) loss[0] = n > 0 ? -s / (float)n : 0.f;
 }
 
 __global__ __launch_bounds__(256) void symm_add_kernel(const float* __restrict__ d, float* __restrict__ g, int n,
@@ -122,19 +144,23 @@ __global__ __launch_bounds__(256) void symm_add_kernel(const float* __restrict__
   }
 }
 
-// dx[b_i, :, p_i] = (dA_i - A_i <A_i, dA_i>) / ||x_i||   (anchors are distinct pixels: plain scatter)
+// dx[b_i, :, p_i] = (dA_i - A_i <A_i, dA_i>) / ||x_i||   (anchors are distinct pixels per half: plain scatter)
 __global__ __launch_bounds__(256) void l2norm_bwd_scatter_kernel(const float* __restrict__ dA, const float* __restrict__ A,
-                                                                 const float* __restrict__ norms,
-                                                                 const int* __restrict__ ib, const int* __restrict__ ip,
-                                                                 int N, int C, float* __restrict__ dx, long long sb,
-                                                                 long long sc, long long sp) {
+                                                                 const float* __restrict__ norms, const int* __restrict__ header,
+                                                                 const int* __restrict__ ib, const int* __restrict__ ip, int cap, int N,
+                                                                 int n_match, int C,
+                                                                 float* __restrict__ dxm, long long msb, long long msc, long long msp,
+                                                                 float* __restrict__ dxs, long long ssb, long long ssc, long long ssp) {
   const int lane = threadIdx.x & 63;
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < N; i += gridDim.x * 4) {
+  const AnchorCount cnt = anchor_count(header, cap, N, n_match);
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < cnt.n; i += gridDim.x * 4) {
     float dot = 0.f;
     for (int c = lane; c < C; c += 64) dot += A[(size_t)i * C + c] * dA[(size_t)i * C + c];
     dot = wave_sum(dot);
     const float inv = 1.f / norms[i];
-    float* dst = dx + (long long)ib[i] * sb + (long long)ip[i] * sp;
+    const bool m = i < cnt.n_match;
+    const long long sc = m ? msc : ssc;
+    float* dst = m ? dxm + (long long)ib[i] * msb + (long long)ip[i] * msp : dxs + (long long)ib[i] * ssb + (long long)ip[i] * ssp;
     for (int c = lane; c < C; c += 64) dst[(long long)c * sc] = (dA[(size_t)i * C + c] - A[(size_t)i * C + c] * dot) * inv;
   }
 }
@@ -318,84 +344,10 @@ __global__ __launch_bounds__(kSelThreads) void contrast_select_kernel(const int*
   }
 }
 
-// one wave per row of A; rows >= n are zero
-__global__ __launch_bounds__(256) void gather_l2norm_dev_kernel(const float* __restrict__ xm, long long msb, long long msc, long long msp,
-                                                                const float* __restrict__ xs, long long ssb, long long ssc, long long ssp,
-                                                                const int* __restrict__ header, const int* __restrict__ ib,
-                                                                const int* __restrict__ ip, int cap, int rows, int C, float eps,
-                                                                float* __restrict__ A, float* __restrict__ norms) {
-  const int lane = threadIdx.x & 63;
-  int n = header[0];
-  n = n < 0 ? 0 : (n > cap ? cap : n);
-  const int n_match = header[1];
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < rows; i += gridDim.x * 4) {
-    if (i >= n) {
-      for (int c = lane; c < C; c += 64) A[(size_t)i * C + c] = 0.f;
-      if (lane == 0) norms[i] = 1.f;
-      continue;
-    }
-    const bool m = i < n_match;
-    const long long sc = m ? msc : ssc;
-    const float* src = m ? xm + (long long)ib[i] * msb + (long long)ip[i] * msp : xs + (long long)ib[i] * ssb + (long long)ip[i] * ssp;
-    float q = 0.f;
-    for (int c = lane; c < C; c += 64) { const float v = src[(long long)c * sc]; q += v * v; }
-    const float nrm = fmaxf(sqrtf(wave_sum(q)), eps);
-    for (int c = lane; c < C; c += 64) A[(size_t)i * C + c] = src[(long long)c * sc] / nrm;
-    if (lane == 0) norms[i] = nrm;
-  }
-}
-
-__global__ __launch_bounds__(256) void infonce_rows_dev_kernel(const float* __restrict__ S, const int* __restrict__ lab,
-                                                               const int* __restrict__ header, int cap, int ld, float eps,
-                                                               float* __restrict__ out_rows, float* __restrict__ dS, float grad_scale) {
-  __shared__ float red[4];
-  int n = header[0];
-  n = n < 0 ? 0 : (n > cap ? cap : n);
-  infonce_row(S, lab, n, ld, eps, out_rows, dS, grad_scale, red);
-}
-
-__global__ __launch_bounds__(256) void mean_neg_dev_kernel(const float* rows, const int* __restrict__ header, int cap, float* loss) {
-  __shared__ float red[4];
-  int n = header[0];
-  n = n < 0 ? 0 : (n > cap ? cap : n);
-  float s = 0.f;
-  for (int j = threadIdx.x; j < n; j += 256) s += rows[j];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) loss[0] = n > 0 ? -s / (float)n : 0.f;
-}
-
-__global__ __launch_bounds__(256) void l2norm_bwd_scatter_dev_kernel(const float* __restrict__ dA, const float* __restrict__ A,
-                                                                     const float* __restrict__ norms, const int* __restrict__ header,
-                                                                     const int* __restrict__ ib, const int* __restrict__ ip, int cap, int C,
-                                                                     float* __restrict__ dxm, long long msb, long long msc, long long msp,
-                                                                     float* __restrict__ dxs, long long ssb, long long ssc, long long ssp) {
-  const int lane = threadIdx.x & 63;
-  int n = header[0];
-  n = n < 0 ? 0 : (n > cap ? cap : n);
-  const int n_match = header[1];
-  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
-    float dot = 0.f;
-    for (int c = lane; c < C; c += 64) dot += A[(size_t)i * C + c] * dA[(size_t)i * C + c];
-    dot = wave_sum(dot);
-    const float inv = 1.f / norms[i];
-    const bool m = i < n_match;
-    const long long sc = m ? msc : ssc;
-    float* dst = m ? dxm + (long long)ib[i] * msb + (long long)ip[i] * msp : dxs + (long long)ib[i] * ssb + (long long)ip[i] * ssp;
-    for (int c = lane; c < C; c += 64) dst[(long long)c * sc] = (dA[(size_t)i * C + c] - A[(size_t)i * C + c] * dot) * inv;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // The two ends of the chain on the training tape's fusion map as it lies in memory: x / g = [2B][HW][ld] of the compute dtype
 // (ld >= C, the match half first).  Anchor i lives in image idx_b[i] (i < n_match) or B + idx_b[i]; the count comes from the
 // device sampler's header or, header == nullptr, from the host.  One wave per anchor row, 16-byte vectors, f32 arithmetic.
-struct AnchorCount { int n, n_match; };
-__device__ __forceinline__ AnchorCount anchor_count(const int* __restrict__ header, int cap, int N, int n_match) {
-  if (!header) return {N, n_match};
-  int n = header[0];
-  n = n < 0 ? 0 : (n > cap ? cap : n);
-  return {n, header[1]};
-}
 // first element of anchor i's row, or -1 when the plan entry does not address a pixel of the map (rows >= n hold -1)
 __device__ __forceinline__ long long anchor_row(const int* __restrict__ ib, const int* __restrict__ ip, int i, int n_match, int B,
                                                 int HW, int ld) {
@@ -505,48 +457,61 @@ extern "C" int cavp_label_nearest(const int64_t* gt, int32_t* out, int32_t B, in
   CHECK_LAUNCH();
 }
 
-extern "C" int cavp_gather_l2norm(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_p,
-                                  const int32_t* idx_b, const int32_t* idx_p, int32_t N, int32_t C, float eps, float* A,
-                                  float* norms, void* stream) {
-  if (!x || !idx_b || !idx_p || !A || !norms || N <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
-  gather_l2norm_kernel<<<(N + 3) / 4, 256, 0, (hipStream_t)stream>>>(x, stride_b, stride_c, stride_p, idx_b, idx_p, N, C, eps, A, norms);
+// shared argument check of the chain's strided-f32 ends: the count from `header` (cap rows of plan) or from (N, n_match).
+// map_m / map_s: the two feature maps (gather) or their gradients (scatter); rows0 / rows1: the [rows][C] buffers of the call
+// (gather: A twice; scatter: dA and A)
+static int contrast_ends_args_ok(const float* map_m, const float* map_s, const int32_t* header, const int32_t* idx_b,
+                                 const int32_t* idx_p, int cap, int N, int n_match, int C, const float* rows0, const float* rows1,
+                                 const float* norms) {
+  if (!map_m || !map_s || !idx_b || !idx_p || !rows0 || !rows1 || !norms || C <= 0) return CAVP_ERR_BAD_ARG;
+  if (header ? cap <= 0 : (N <= 0 || n_match < 0 || n_match > N)) return CAVP_ERR_BAD_ARG;
+  return CAVP_OK;
+}
+
+extern "C" int cavp_gather_l2norm(const float* xm, int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, const float* xs,
+                                  int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p, const int32_t* header,
+                                  const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match, int32_t rows,
+                                  int32_t C, float eps, float* A, float* norms, void* stream) {
+  const int st = contrast_ends_args_ok(xm, xs, header, idx_b, idx_p, cap, N, n_match, C, A, A, norms);
+  if (st != CAVP_OK) return st;
+  if (rows < (header ? cap : N)) return CAVP_ERR_BAD_ARG;
+  gather_l2norm_kernel<<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>(xm, m_stride_b, m_stride_c, m_stride_p, xs, s_stride_b, s_stride_c,
+                                                                        s_stride_p, header, idx_b, idx_p, cap, N, n_match, rows, C, eps,
+                                                                        A, norms);
   CHECK_LAUNCH();
 }
 
-extern "C" int cavp_infonce_rows(const float* S, const int32_t* labels, int32_t N, int32_t ld, float eps, float* row_mlpp,
-                                 float* loss, float* dS, float grad_scale, void* stream) {
-  if (!S || !labels || !row_mlpp || !loss || N <= 0 || ld < N) return CAVP_ERR_BAD_ARG;
+extern "C" int cavp_infonce_rows(const float* S, const int32_t* labels, const int32_t* header, int32_t cap, int32_t N, int32_t ld,
+                                 float eps, float* row_mlpp, float* loss, float* dS, float grad_scale, void* stream) {
+  if (!S || !labels || !row_mlpp || !loss || (header ? cap <= 0 : N <= 0) || ld < (header ? cap : N)) return CAVP_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  infonce_rows_kernel<<<ld, 256, 0, s>>>(S, labels, N, ld, eps, row_mlpp, dS, grad_scale);
-  mean_neg_kernel<<<1, 256, 0, s>>>(row_mlpp, N, loss);
+  infonce_rows_kernel<<<ld, 256, 0, s>>>(S, labels, header, cap, N, ld, eps, row_mlpp, dS, grad_scale);
+  mean_neg_kernel<<<1, 256, 0, s>>>(row_mlpp, header, cap, N, loss);
   CHECK_LAUNCH();
 }
 
-extern "C" int cavp_symm_add(const float* d, float* g, int32_t n, float scale, void* stream) {
+extern "C" int cavp_symm_add(const float* d, float* g, int32_t n, float scale, const float* scale_dev, void* stream) {
   if (!d || !g || n <= 0) return CAVP_ERR_BAD_ARG;
-  long long nb = ((long long)n * n + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  symm_add_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(d, g, n, scale, nullptr);
-  CHECK_LAUNCH();
-}
-
-extern "C" int cavp_symm_add_scaled(const float* d, float* g, int32_t n, float scale, const float* scale_dev, void* stream) {
-  if (!d || !g || !scale_dev || n <= 0) return CAVP_ERR_BAD_ARG;
   long long nb = ((long long)n * n + 255) / 256;
   if (nb > 8192) nb = 8192;
   symm_add_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(d, g, n, scale, scale_dev);
   CHECK_LAUNCH();
 }
 
-extern "C" int cavp_l2norm_bwd_scatter(const float* dA, const float* A, const float* norms, const int32_t* idx_b,
-                                       const int32_t* idx_p, int32_t N, int32_t C, float* dx, int64_t stride_b,
-                                       int64_t stride_c, int64_t stride_p, void* stream) {
-  if (!dA || !A || !norms || !idx_b || !idx_p || !dx || N <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
-  l2norm_bwd_scatter_kernel<<<(N + 3) / 4, 256, 0, (hipStream_t)stream>>>(dA, A, norms, idx_b, idx_p, N, C, dx, stride_b, stride_c, stride_p);
+extern "C" int cavp_l2norm_bwd_scatter(const float* dA, const float* A, const float* norms, const int32_t* header, const int32_t* idx_b,
+                                       const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match, int32_t C, float* dxm,
+                                       int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, float* dxs, int64_t s_stride_b,
+                                       int64_t s_stride_c, int64_t s_stride_p, void* stream) {
+  const int st = contrast_ends_args_ok(dxm, dxs, header, idx_b, idx_p, cap, N, n_match, C, dA, A, norms);
+  if (st != CAVP_OK) return st;
+  const int rows = header ? cap : N;
+  l2norm_bwd_scatter_kernel<<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>(dA, A, norms, header, idx_b, idx_p, cap, N, n_match, C, dxm,
+                                                                             m_stride_b, m_stride_c, m_stride_p, dxs, s_stride_b,
+                                                                             s_stride_c, s_stride_p);
   CHECK_LAUNCH();
 }
 
-// ---- ABI 14: device-side sampling and the device-n chain ----
+// ---- ABI 14: device-side sampling ----
 extern "C" size_t cavp_contrast_sample_work_bytes(int32_t max_classes) {
   if (max_classes < 1 || max_classes > 254) return 0;
   return ((size_t)kCountBlocks * kHistStride + 3 * (size_t)(max_classes + 2)) * sizeof(int32_t);
@@ -568,37 +533,6 @@ extern "C" int cavp_contrast_sample(const int32_t* gm, const int32_t* gs, int64_
                                          gl + 2 * G);
   contrast_select_kernel<<<G, kSelThreads, 0, s>>>(gm, gs, total, HW, ignore_idx, header, gl, gl + G, gl + 2 * G, cap, idx_b, idx_p,
                                                    labels);
-  CHECK_LAUNCH();
-}
-
-extern "C" int cavp_gather_l2norm_dev(const float* xm, int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, const float* xs,
-                                      int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p, const int32_t* header,
-                                      const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t rows, int32_t C, float eps,
-                                      float* A, float* norms, void* stream) {
-  if (!xm || !xs || !header || !idx_b || !idx_p || !A || !norms || cap <= 0 || rows < cap || C <= 0) return CAVP_ERR_BAD_ARG;
-  gather_l2norm_dev_kernel<<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>(xm, m_stride_b, m_stride_c, m_stride_p, xs, s_stride_b,
-                                                                            s_stride_c, s_stride_p, header, idx_b, idx_p, cap, rows, C,
-                                                                            eps, A, norms);
-  CHECK_LAUNCH();
-}
-
-extern "C" int cavp_infonce_rows_dev(const float* S, const int32_t* labels, const int32_t* header, int32_t cap, int32_t ld, float eps,
-                                     float* row_mlpp, float* loss, float* dS, float grad_scale, void* stream) {
-  if (!S || !labels || !header || !row_mlpp || !loss || cap <= 0 || ld < cap) return CAVP_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  infonce_rows_dev_kernel<<<ld, 256, 0, s>>>(S, labels, header, cap, ld, eps, row_mlpp, dS, grad_scale);
-  mean_neg_dev_kernel<<<1, 256, 0, s>>>(row_mlpp, header, cap, loss);
-  CHECK_LAUNCH();
-}
-
-extern "C" int cavp_l2norm_bwd_scatter_dev(const float* dA, const float* A, const float* norms, const int32_t* header,
-                                           const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t C, float* dxm,
-                                           int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, float* dxs, int64_t s_stride_b,
-                                           int64_t s_stride_c, int64_t s_stride_p, void* stream) {
-  if (!dA || !A || !norms || !header || !idx_b || !idx_p || !dxm || !dxs || cap <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
-  l2norm_bwd_scatter_dev_kernel<<<(cap + 3) / 4, 256, 0, (hipStream_t)stream>>>(dA, A, norms, header, idx_b, idx_p, cap, C, dxm,
-                                                                                m_stride_b, m_stride_c, m_stride_p, dxs, s_stride_b,
-                                                                                s_stride_c, s_stride_p);
   CHECK_LAUNCH();
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CAVP_ABI_VERSION 15
+#define CAVP_ABI_VERSION 16
 
 typedef enum { CAVP_F32 = 0, CAVP_BF16 = 1, CAVP_I64 = 2 /* ABI 13: metrics inputs only */ } cavp_dtype_t;
 typedef enum { CAVP_ACT_NONE = 0, CAVP_ACT_RELU = 1, CAVP_ACT_LEAKY = 2, CAVP_ACT_GELU = 3 } cavp_act_t;
@@ -484,21 +484,30 @@ int cavp_mel_frontend(const float* wave, int32_t N, int32_t A, const float* wind
  * (contrastive_aud.py:18-22 `F.interpolate(gt.unsqueeze(1).float(), size, mode='nearest')`): only B*h*w int32 labels travel to the
  * host for the class-balanced sampling instead of the full-resolution int64 maps. */
 int cavp_label_nearest(const int64_t* gt, int32_t* out, int32_t B, int32_t H, int32_t W, int32_t h, int32_t w, void* stream);
-/* A[i] = x[b_i, :, p_i] / max(||.||, eps); x addressed by element strides (works for NCHW memory and for the NHWC
- * memory behind out_fusion); also saves the norms (F.normalize, contrastive_aud.py:25-26 + gathers :97-139). */
-int cavp_gather_l2norm(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_p, const int32_t* idx_b,
-                       const int32_t* idx_p, int32_t N, int32_t C, float eps, float* A, float* norms, void* stream);
-/* info_nce (contrastive_aud.py:41-74) on S[ld][ld] (already / temperature): row_mlpp[i], loss[0] = -mean(row_mlpp);
- * optional dS = grad_scale * dloss/dS (zero in the padding rows / columns >= N). */
-int cavp_infonce_rows(const float* S, const int32_t* labels, int32_t N, int32_t ld, float eps, float* row_mlpp,
-                      float* loss, float* dS, float grad_scale, void* stream);
-int cavp_symm_add(const float* d, float* g, int32_t n, float scale, void* stream); /* g = (d + d^T) * scale */
-/* g = (d + d^T) * scale * scale_dev[0]: the loss's upstream gradient (a device scalar in torch.autograd) stays on the device -
- * reading it on the host stalled the launch queue behind the whole forward pass (config #5, trainer_cavp_vpo_mono.py:178-190) */
-int cavp_symm_add_scaled(const float* d, float* g, int32_t n, float scale, const float* scale_dev, void* stream);
-int cavp_l2norm_bwd_scatter(const float* dA, const float* A, const float* norms, const int32_t* idx_b,
-                            const int32_t* idx_p, int32_t N, int32_t C, float* dx, int64_t stride_b, int64_t stride_c,
-                            int64_t stride_p, void* stream);
+/* The chain's kernels take the anchor count from `header` on the device (the device sampler's plan below: n = clamp(header[0], 0,
+ * cap), n_match = header[1]; N / n_match ignored, cap > 0) or, header == NULL, from the host: (N, n_match), N > 0,
+ * 0 <= n_match <= N.  Index and label arrays hold at least cap rows with a header, at least N without.  Rows < n_match read /
+ * write the match tensor, the others the shuffle one. */
+/* A[i] = x[b_i, :, p_i] / max(||.||, eps); xm / xs addressed by element strides (works for NCHW memory and for the NHWC
+ * memory behind out_fusion); also saves the norms (F.normalize, contrastive_aud.py:25-26 + gathers :97-139).  rows (>= cap
+ * resp. N, the leading dimension of A / S): rows >= n of A are zero-filled, norms 1. */
+int cavp_gather_l2norm(const float* xm, int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, const float* xs,
+                       int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p, const int32_t* header, const int32_t* idx_b,
+                       const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match, int32_t rows, int32_t C, float eps, float* A,
+                       float* norms, void* stream);
+/* info_nce (contrastive_aud.py:41-74) on S[ld][ld] (already / temperature; ld >= cap resp. N): row_mlpp[i], loss[0] =
+ * -mean(row_mlpp), 0 when n == 0; columns / rows >= n of S are ignored; optional dS = grad_scale * dloss/dS, zero outside [n][n]. */
+int cavp_infonce_rows(const float* S, const int32_t* labels, const int32_t* header, int32_t cap, int32_t N, int32_t ld, float eps,
+                      float* row_mlpp, float* loss, float* dS, float grad_scale, void* stream);
+/* g = (d + d^T) * scale * (scale_dev ? scale_dev[0] : 1): the loss's upstream gradient (a device scalar in torch.autograd) stays on
+ * the device - reading it on the host stalled the launch queue behind the whole forward pass (config #5,
+ * trainer_cavp_vpo_mono.py:178-190) */
+int cavp_symm_add(const float* d, float* g, int32_t n, float scale, const float* scale_dev, void* stream);
+/* dx[b_i, :, p_i] = (dA_i - A_i <A_i, dA_i>) / norms[i] for the rows < n; nothing else of dxm / dxs is written. */
+int cavp_l2norm_bwd_scatter(const float* dA, const float* A, const float* norms, const int32_t* header, const int32_t* idx_b,
+                            const int32_t* idx_p, int32_t cap, int32_t N, int32_t n_match, int32_t C, float* dxm, int64_t m_stride_b,
+                            int64_t m_stride_c, int64_t m_stride_p, float* dxs, int64_t s_stride_b, int64_t s_stride_c,
+                            int64_t s_stride_p, void* stream);
 
 /* ---- ABI 14: device-side anchor sampling (opt-in; contrastive_aud.py:76-141 with a counter-based generator) ----
  * The selection rule of extraction_samples with Philox4x32-10 in place of torch.randperm, so that the whole loss step runs
@@ -518,19 +527,6 @@ size_t cavp_contrast_sample_work_bytes(int32_t max_classes);
 int cavp_contrast_sample(const int32_t* gm, const int32_t* gs, int64_t total, int32_t HW, int32_t ignore_idx, int32_t max_views,
                          int32_t max_classes, int64_t* state, int32_t* header, int32_t* work, int32_t* idx_b, int32_t* idx_p,
                          int32_t* labels, void* stream);
-/* The chain above with the anchor count read from `header` on the device.  rows (>= cap, the leading dimension of A / S) is
- * static: rows >= n of A are zero-filled (norms 1), columns / rows >= n of S are ignored and dS is zero outside [n][n], the loss
- * is 0 when n == 0, and the scatter skips rows >= n.  Rows < n_match read / write the match tensor, the others the shuffle one. */
-int cavp_gather_l2norm_dev(const float* xm, int64_t m_stride_b, int64_t m_stride_c, int64_t m_stride_p, const float* xs,
-                           int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p, const int32_t* header,
-                           const int32_t* idx_b, const int32_t* idx_p, int32_t cap, int32_t rows, int32_t C, float eps, float* A,
-                           float* norms, void* stream);
-int cavp_infonce_rows_dev(const float* S, const int32_t* labels, const int32_t* header, int32_t cap, int32_t ld, float eps,
-                          float* row_mlpp, float* loss, float* dS, float grad_scale, void* stream);
-int cavp_l2norm_bwd_scatter_dev(const float* dA, const float* A, const float* norms, const int32_t* header, const int32_t* idx_b,
-                                const int32_t* idx_p, int32_t cap, int32_t C, float* dxm, int64_t m_stride_b, int64_t m_stride_c,
-                                int64_t m_stride_p, float* dxs, int64_t s_stride_b, int64_t s_stride_c, int64_t s_stride_p,
-                                void* stream);
 
 /* ---- The two ends of the chain on the training tape's fusion map (two entry points added to ABI 15; nothing else changed) ----
  * x / g: the map as it lies in memory, [2B][HW][ld] of `dtype` (CAVP_F32 / CAVP_BF16), ld >= C, the match half first.  Anchor row i

@@ -1,6 +1,7 @@
 """ContrastLoss with the opt-in device sampler (ContrastLoss.use_device_sampler): the numpy restatement of the sampling
 specification against the reference's rules (CPU), and the MI355X path against the restatement, against the oracle's InfoNCE on the
 sampled anchors, against the reference-anchored oracle where the sample is forced, and inside a captured hipGraph (gpu)."""
+import functools
 import math
 
 import numpy as np
@@ -274,6 +275,87 @@ def test_gpu_loss_and_gradients_for_the_sampled_plan(layout, mem):
     plan = _download(crit)
     _assert_plan_equal(plan, R.plan(_reduce(gt, size), _reduce(gs, size), IGN, max_views, max_classes, 3, 0))
     _assert_loss_and_grads(loss, emd.grad, esd.grad, *_cpu_reference(em, es, plan))
+
+
+# ---- the chain's strided-f32 kernels on a hand-built plan, with the anchor count from the host (SamplePlan) and from a plan header
+# (DevicePlan at capacity OP_CAP).  C = 40: less than one wave and no multiple of 64; 304: the product width.
+OP_B, OP_HW, OP_N, OP_N_MATCH, OP_CAP = 2, (5, 7), 37, 21, 48
+OP_CASES = [(mode, mem, C, n, n_match)
+            for mode in ("host", "header") for mem in ("nchw", "nhwc_view") for C in (40, 304)
+            for n, n_match in ((OP_N, OP_N_MATCH), (OP_N, 0), (OP_N, OP_N), (0, 0))     # (one half empty) x 2; an empty plan
+            if n or mode == "header"]                                                  # (only a header can say n = 0)
+
+
+@functools.lru_cache(maxsize=None)
+def _op_inputs(C):
+    g = torch.Generator().manual_seed(100 + C)
+    em = torch.randn((OP_B, C) + OP_HW, generator=g)
+    return em, em * 0.5 + torch.randn((OP_B, C) + OP_HW, generator=g)
+
+
+@functools.lru_cache(maxsize=None)
+def _op_anchors(n, n_match):
+    """n anchors: distinct pixels per half, labels in {0, 1, 2}; in the layout of _download()."""
+    rng = np.random.default_rng(5)
+    npix = OP_B * OP_HW[0] * OP_HW[1]
+    idx = np.concatenate([rng.permutation(npix)[:n_match], rng.permutation(npix)[:n - n_match]])
+    b, p = np.divmod(idx, OP_HW[0] * OP_HW[1])
+    return {"header": np.array([n, n_match, 0, 0], dtype=np.int32), "idx_b": b.astype(np.int32), "idx_p": p.astype(np.int32),
+            "labels": rng.integers(0, 3, n).astype(np.int32)}
+
+
+@functools.lru_cache(maxsize=None)
+def _op_reference(C, n, n_match):
+    """(loss, d_match, d_shuffle) of the reference-pinned oracle on these anchors; an empty plan: loss 0, no gradient."""
+    em, es = _op_inputs(C)
+    if n == 0:
+        return 0.0, torch.zeros_like(em), torch.zeros_like(es)
+    loss, gm, gs = _cpu_reference(em, es, _op_anchors(n, n_match))
+    return loss, torch.zeros_like(em) if gm is None else gm, torch.zeros_like(es) if gs is None else gs
+
+
+def _op_run(mode, mem, C, n, n_match, tail=None):
+    """_InfoNCEFn forward + backward on the plan; tail: what rows >= n of a DevicePlan's arrays hold (-1 or in-range garbage)."""
+    from cavp_amd.contrast import DevicePlan, SamplePlan, _InfoNCEFn
+    em, es = _op_inputs(C)
+    a = _op_anchors(n, n_match)
+    emd, esd = _to_dev(em, mem, True), _to_dev(es, mem, True)
+    if mode == "host":
+        plan = SamplePlan(a["idx_b"], a["idx_p"], a["labels"], n_match)
+    else:
+        rng = np.random.default_rng(6)
+        rows = np.full((3, OP_CAP), -1, dtype=np.int32)
+        if tail == "garbage":
+            rows = np.stack([rng.integers(0, hi, OP_CAP) for hi in (OP_B, OP_HW[0] * OP_HW[1], 3)]).astype(np.int32)
+        rows[:, :n] = a["idx_b"], a["idx_p"], a["labels"]
+        header = np.array([n, n_match, 0, 0, 0, 0, 0, 0], dtype=np.int32)
+        buf = torch.from_numpy(np.concatenate([header, rows.reshape(-1)])).to(DEV)
+        ib, ip, lab = buf[8:].view(3, OP_CAP)
+        plan = DevicePlan(buf[:8], ib, ip, lab, OP_CAP, None, None, None)
+    loss = _InfoNCEFn.apply(emd, esd, plan, TEMP, 1e-12)
+    loss.backward()
+    torch.cuda.synchronize()
+    return loss.detach(), emd.grad.detach(), esd.grad.detach()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,mem,C,n,n_match", OP_CASES, ids=["-".join(str(v) for v in c) for c in OP_CASES])
+def test_gpu_chain_on_a_hand_built_plan(deterministic, mode, mem, C, n, n_match):
+    loss, gm, gs = _op_run(mode, mem, C, n, n_match, tail="minus1")
+    _assert_loss_and_grads(loss, gm, gs, *_op_reference(C, n, n_match))
+    a = _op_anchors(n, n_match)
+    hw = OP_HW[0] * OP_HW[1]
+    for g, lo, hi in ((gm, 0, n_match), (gs, n_match, n)):          # pixels outside the plan: exactly zero
+        outside = np.ones(OP_B * hw, dtype=bool)
+        outside[a["idx_b"][lo:hi].astype(np.int64) * hw + a["idx_p"][lo:hi]] = False
+        rest = g.cpu().permute(0, 2, 3, 1).reshape(OP_B * hw, C)[torch.from_numpy(outside)]
+        assert rest.numel() > 0 and float(rest.abs().max()) == 0.0
+    if n == 0:
+        assert float(loss.item()) == 0.0 and float(gm.abs().max()) == 0.0 and float(gs.abs().max()) == 0.0
+    if mode == "header":
+        # the rows >= n of the index and label arrays are never read: in-range garbage there changes no bit
+        loss2, gm2, gs2 = _op_run(mode, mem, C, n, n_match, tail="garbage")
+        assert torch.equal(loss, loss2) and torch.equal(gm, gm2) and torch.equal(gs, gs2)
 
 
 def _case_a():

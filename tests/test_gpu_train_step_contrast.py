@@ -126,6 +126,22 @@ def test_unsupported_width_raises():
         contrast_rows_bwd_add(x, plan, idx, A, A, norms)
 
 
+def test_symm_add_takes_the_scale_from_the_host_alone_or_from_a_device_scalar_too():
+    """cavp_symm_add with scale_dev == NULL (the native step's call) and with a device scalar (autograd's upstream gradient)"""
+    import ctypes
+    from cavp_amd import _lib
+    lib = _lib.load()
+    d = torch.arange(16, dtype=torch.float32, device=DEV).reshape(4, 4)
+    up = torch.tensor([3.0], device=DEV)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    for scale_dev, ref in ((None, (d + d.t()) * 0.5), (up, (d + d.t()) * 1.5)):
+        g = torch.empty_like(d)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        assert lib.cavp_symm_add(ptr(d), ptr(g), 4, 0.5, None if scale_dev is None else ptr(scale_dev), st) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(g, ref)       # small integers and halves: exact in f32
+
+
 # --------------------------------------------------------------------------------------------------------------------- step
 CFG = dict(C=3, B=4, hw=(64, 64), lds=[False, False, False])
 

@@ -38,4 +38,4 @@ def test_new_prototypes_are_declared():
         assert name in _lib.PROTOTYPES, name
     assert len(_lib.PROTOTYPES["cavp_optimizer_schedule"][1]) == 2
     assert len(_lib.PROTOTYPES["cavp_optimizer_step_dev"][1]) == 7
-    assert _lib.ABI_VERSION == 15
+    assert _lib.ABI_VERSION == 16

@@ -20,7 +20,7 @@ def test_library_exports_seg_predict_and_abi_15():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, "cavp_seg_predict_nhwc")
     assert "cavp_seg_predict_nhwc" in _lib.PROTOTYPES
-    assert _lib.ABI_VERSION == 15 == _lib.load().cavp_abi_version()
+    assert _lib.ABI_VERSION == 16 == _lib.load().cavp_abi_version()
 
 
 def test_predict_needs_device_tensors():

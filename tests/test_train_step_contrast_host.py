@@ -49,6 +49,52 @@ def test_kernels_reject_bad_arguments_on_the_host():
     assert gather(x=None) == _lib.ERR_BAD_ARG
 
 
+def test_chain_kernels_reject_bad_arguments_on_the_host():
+    """the four entry points of the strided-f32 chain, in both count modes (header / host): checked before any launch"""
+    from cavp_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 64)()
+    idx = (ctypes.c_int32 * 8)()
+    p, i = ctypes.cast(buf, ctypes.c_void_p), ctypes.cast(idx, ctypes.c_void_p)
+
+    def gather(header=None, cap=0, N=4, n_match=2, rows=4, C=16, xm=p, xs=p, ib=i, ip=i, A=p, norms=p):
+        return lib.cavp_gather_l2norm(xm, 64, 1, 16, xs, 64, 1, 16, header, ib, ip, cap, N, n_match, rows, C, 1e-12, A, norms, None)
+
+    def scatter(header=None, cap=0, N=4, n_match=2, C=16, dA=p, A=p, norms=p, ib=i, ip=i, dxm=p, dxs=p):
+        return lib.cavp_l2norm_bwd_scatter(dA, A, norms, header, ib, ip, cap, N, n_match, C, dxm, 64, 1, 16, dxs, 64, 1, 16, None)
+
+    def rows(header=None, cap=0, N=4, ld=4, S=p, labels=i, mlpp=p, loss=p):
+        return lib.cavp_infonce_rows(S, labels, header, cap, N, ld, 1e-12, mlpp, loss, None, 1.0, None)
+
+    for call, operands in ((gather, ("xm", "xs", "ib", "ip", "A", "norms")),
+                           (scatter, ("dA", "A", "norms", "ib", "ip", "dxm", "dxs")), (rows, ("S", "labels", "mlpp", "loss"))):
+        for name in operands:
+            assert call(**{name: None}) == _lib.ERR_BAD_ARG, (call.__name__, name)
+            assert call(header=i, cap=4, **{name: None}) == _lib.ERR_BAD_ARG, (call.__name__, name)
+        for cap in (0, -1):
+            assert call(header=i, cap=cap) == _lib.ERR_BAD_ARG       # header mode: N is ignored, the capacity is not
+        for N in (0, -3):
+            assert call(N=N) == _lib.ERR_BAD_ARG
+    for call in (gather, scatter):
+        assert call(n_match=-1) == _lib.ERR_BAD_ARG
+        assert call(n_match=5) == _lib.ERR_BAD_ARG
+        assert call(C=0) == _lib.ERR_BAD_ARG
+    assert gather(rows=3) == _lib.ERR_BAD_ARG                     # fewer rows of A than the count, in either mode
+    assert gather(header=i, cap=8, rows=7) == _lib.ERR_BAD_ARG
+    assert rows(ld=3) == _lib.ERR_BAD_ARG
+    assert rows(header=i, cap=8, ld=7) == _lib.ERR_BAD_ARG
+
+    for bad in (dict(d=None), dict(g=None), dict(n=0), dict(n=-2)):
+        a = dict(d=p, g=p, n=4)
+        a.update(bad)
+        for scale_dev in (None, p):
+            assert lib.cavp_symm_add(a["d"], a["g"], a["n"], 1.0, scale_dev, None) == _lib.ERR_BAD_ARG
+    # scale_dev == NULL is a legal call: it gets past the checks, to the launch.  Host memory must not reach a kernel, so this is
+    # probed only where there is no device to launch on; with one, tests/test_gpu_train_step_contrast.py makes the call on device memory
+    if not torch.cuda.is_available():
+        assert lib.cavp_symm_add(p, p, 4, 1.0, None, None) != _lib.ERR_BAD_ARG
+
+
 def test_anchor_rows_addresses_both_halves():
     from cavp_amd._lib import CavpError
     from cavp_amd.contrast import anchor_rows
