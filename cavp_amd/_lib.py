@@ -173,6 +173,14 @@ PROTOTYPES = {
     "cavp_aug_plan": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cavp_aug_contrast_mean": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "cavp_aug_render": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ---- frame augmentation, resize variant: a second resize instead of pad + crop (added to ABI 16) ----
+    "cavp_aug_plan_resize": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_aug_resize_store": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "cavp_aug_resize_render": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ---- label stage: class-index remap, class vector, binary collapse (added to ABI 16) ----
+    "cavp_labels_presence": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp]),
+    "cavp_labels_scan": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_labels_expand": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -28,12 +28,23 @@ crops that is "pad to the crop".  Where torchvision would raise because the padd
 counted in a device-side `bad` counter (as are staged sizes outside 1 <= h <= Hs, 1 <= w <= Ws and `params` fields out of range)
 and rendered from clamped coordinates; nothing is read out of bounds; check() raises.
 
-Out of scope: decoding (stays on the host); the VPO datasets' class-index remap of the mask (done there after the transform);
-the avss dataset's `resize_flag=True` variant (a plain resize instead of pad + crop).  The five copies of visual_aug.py were
+`resize=True` is the avss data set's `resize_flag=True` variant (visual_aug.py:31-35,71-72,81-82; main_avss_resize.py): flip, random
+scale and jitter as above, then the image is RESIZED to `crop` (BICUBIC frame, NEAREST mask) instead of padded and cropped;
+eval_() resizes too.  The same seed and offset give the same flip, scale and jitter draws (params[:, 0:10]) as the crop variant;
+the crop origin is not drawn, top = left = 0, pad_fill is unused and no sample is "too small".  The frame goes through PIL's
+sequence step by step - two-pass BICUBIC to the scaled size, the jitter chain on that uint8 image, a second two-pass BICUBIC to
+H x W - so the scaled image is stored once in a scratch allocated with the device state: max_batch x floor(Hs * max(scales)) x
+floor(Ws * max(scales)) x 4 bytes (52 MB at max_batch 32, stage 640 x 640, the AVS scales).  The second pass holds 34 taps:
+stage_side * max(scales) <= 8 * crop_side on both axes (eval_: stage_side <= 8 * crop_side), the constructor raises otherwise;
+`crop` may be larger than the stage (an upscale).  Launches: plan_resize -> contrast_mean (only with jitter) -> resize_store ->
+resize_render; eval_: plan_resize -> resize_render on the staged frames.
+
+Out of scope: decoding (stays on the host).  The data sets' class-index remap of the mask and their image labels are
+cavp_amd/labels.py (LabelStage), which takes out.label.  The five copies of visual_aug.py were
 compared: vpo_mono/single_source and vpo_stereo/single_source only add the "avs_sailent" setup name (= jitter=None, scales
 (0.5, 0.75, 1.0)); vpo_stereo/multi_source additionally returns the flip decision, which is out.params[:, 0] here (the stereo
-trainers swap the audio channels with it); avss adds the resize_flag branch.  With resize_flag off all five compute the same
-pixels."""
+trainers swap the audio channels with it); avss adds the resize_flag branch (`resize=True`).  With resize_flag off all five compute
+the same pixels."""
 from __future__ import annotations
 
 import ctypes as C
@@ -46,6 +57,7 @@ from . import _lib
 from .ops import _ptr, _stream
 
 MAX_BATCH, MAX_SCALES = 1024, 16
+RESIZE_MAX_RATIO = 8        # in / out of the resize variant's second pass, per axis (34 taps)
 COCO_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75, 2.0)
 AVS_SCALES = (0.5, 0.75, 1.0)
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -82,17 +94,23 @@ def make_params(flip, scale, top, left, order=(0, 1, 2, 3), brightness=1.0, cont
 class FrameAugment:
     """See the module docstring.  Limits: B <= max_batch <= 1024; at most 16 scales, each a multiple of 1/64 in [0.5, 4] (both
     reference lists qualify; it makes the reference's int(w * s) an exact integer expression on the device and bounds the filter
-    taps); crop <= stage.  Inputs must be contiguous device tensors and are never modified."""
+    taps); crop <= stage (resize=True: any crop with stage_side * max(scales) <= 8 * crop_side).  Inputs must be contiguous device
+    tensors and are never modified."""
 
     def __init__(self, crop, mean=IMAGENET_MEAN, std=IMAGENET_STD, scales=COCO_SCALES, jitter=(.5, .5, .5, .25), pad_fill=None,
-                 seed: int = 0, device=None, max_batch: int = 64, stage=None):
+                 seed: int = 0, device=None, max_batch: int = 64, stage=None, resize: bool = False):
         E = _lib.CavpError
         if stage is None or len(tuple(stage)) != 2 or len(tuple(crop)) != 2:
             raise E("FrameAugment: crop=(H, W) and stage=(Hs, Ws) are required")
         self.H, self.W = (int(v) for v in crop)
         self.Hs, self.Ws = (int(v) for v in stage)
-        if self.H < 1 or self.W < 1 or self.H > self.Hs or self.W > self.Ws:
+        self.resize = bool(resize)
+        if self.H < 1 or self.W < 1 or (not self.resize and (self.H > self.Hs or self.W > self.Ws)):
             raise E(f"FrameAugment: crop {(self.H, self.W)} must be positive and fit the stage {(self.Hs, self.Ws)}")
+        if self.resize and (self.H > 16384 or self.W > 16384):
+            raise E("FrameAugment: output sides above 16384 are not supported")
+        if self.resize and pad_fill is not None:
+            raise E("FrameAugment: resize=True has no pad: pad_fill must be left at its default")
         if self.Hs > 16384 or self.Ws > 16384:
             raise E("FrameAugment: stage sides above 16384 are not supported")
         if not 1 <= int(max_batch) <= MAX_BATCH:
@@ -108,6 +126,11 @@ class FrameAugment:
                 raise E(f"FrameAugment: scale {s} outside [0.5, 4]")
         self.scales = scales
         self._scales64 = (C.c_int32 * len(scales))(*[int(s * 64) for s in scales])
+        # the resize variant's scaled image at its largest (floor(side * s) is exact: s is a multiple of 1/64)
+        self._mh, self._mw = (self.Hs * max(self._scales64)) >> 6, (self.Ws * max(self._scales64)) >> 6
+        if self.resize and (self._mh > RESIZE_MAX_RATIO * self.H or self._mw > RESIZE_MAX_RATIO * self.W):
+            raise E(f"FrameAugment: resize=True reduces by at most {RESIZE_MAX_RATIO} per axis (34 filter taps): stage {(self.Hs, self.Ws)} "
+                    f"x scale {max(scales)} = {(self._mh, self._mw)} exceeds {RESIZE_MAX_RATIO} x crop {(self.H, self.W)}")
         if len(mean) != 3 or len(std) != 3 or any(not float(s) > 0 for s in std):
             raise E("FrameAugment: mean and std have three entries, std > 0")
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
@@ -135,6 +158,7 @@ class FrameAugment:
             self._state = torch.zeros(4, dtype=torch.int64, device=dev)       # {seed, offset, bad_inputs, reserved}
             self._near = torch.empty((self.max_batch, self.H + self.W), dtype=torch.int32, device=dev)
             self._lsum = torch.zeros(self.max_batch, dtype=torch.int64, device=dev)
+            self._scratch = torch.empty((self.max_batch, self._mh, self._mw), dtype=torch.int32, device=dev) if self.resize else None
             self.manual_seed(self._seed)
         return self._state
 
@@ -185,8 +209,11 @@ class FrameAugment:
                 raise E(f"FrameAugment: {name} must be contiguous")
         return B
 
-    def _run(self, frames, masks, sizes, params, out, identity, launches=("plan", "mean", "render")):
-        """launches: the subset to issue (tools/bench_augment.py times each alone, on the table the last plan left in `out`)."""
+    def _run(self, frames, masks, sizes, params, out, identity, launches=None):
+        """launches: the subset to issue (tools/bench_augment.py times each alone, on the table the last plan left in `out`); None =
+        all of ("plan", "mean", "render"), with "store" in front of "render" for resize=True."""
+        if launches is None:
+            launches = ("plan", "mean", "store", "render") if self.resize else ("plan", "mean", "render")
         B = self._check_inputs(frames, masks, sizes, params)
         state = self._ensure()
         dev = self.device
@@ -199,6 +226,8 @@ class FrameAugment:
         lib = _lib.load()
         st = C.c_void_p(_stream())
         jit = 0 if identity or self.jitter is None else 1
+        if self.resize:
+            return self._run_resize(lib, st, frames, masks, sizes, params, out, identity, jit, B, launches)
         if "plan" in launches:
             _lib.check(lib.cavp_aug_plan(_ptr(sizes), B, self.Hs, self.Ws, self.H, self.W, self._scales64, len(self.scales), jit,
                                          1 if identity else 0, _ptr(params), _ptr(state), _ptr(out.params), _ptr(self._near),
@@ -213,6 +242,30 @@ class FrameAugment:
         self._last = out
         return out
 
+    def _run_resize(self, lib, st, frames, masks, sizes, params, out, identity, jit, B, launches):
+        """The resize variant's launches (module docstring); `launches` as in _run, with "store" for the scratch pass."""
+        if identity and (self.Hs > RESIZE_MAX_RATIO * self.H or self.Ws > RESIZE_MAX_RATIO * self.W):
+            raise _lib.CavpError(f"FrameAugment: eval_ with resize=True reduces by at most {RESIZE_MAX_RATIO} per axis: stage "
+                                 f"{(self.Hs, self.Ws)} exceeds {RESIZE_MAX_RATIO} x crop {(self.H, self.W)}")
+        state, smax = self._state, max(self._scales64)
+        if "plan" in launches:
+            _lib.check(lib.cavp_aug_plan_resize(_ptr(sizes), B, self.Hs, self.Ws, self.H, self.W, self._scales64, len(self.scales), jit,
+                                                1 if identity else 0, _ptr(params), _ptr(state), _ptr(out.params), _ptr(self._near),
+                                                _ptr(self._lsum), st), "cavp_aug_plan_resize")
+        if jit and "mean" in launches:
+            _lib.check(lib.cavp_aug_contrast_mean(_ptr(frames), _ptr(sizes), B, self.Hs, self.Ws, smax, _ptr(out.params),
+                                                  _ptr(self._lsum), st), "cavp_aug_contrast_mean")
+        if not identity and "store" in launches:
+            _lib.check(lib.cavp_aug_resize_store(_ptr(frames), _ptr(sizes), B, self.Hs, self.Ws, smax, jit, _ptr(out.params),
+                                                 _ptr(self._lsum), _ptr(self._scratch), st), "cavp_aug_resize_store")
+        if "render" in launches:
+            src = frames if identity else self._scratch
+            _lib.check(lib.cavp_aug_resize_render(_ptr(src), 1 if identity else 0, _ptr(masks), _ptr(sizes), B, self.Hs, self.Ws, smax,
+                                                  self.H, self.W, self._mean3, self._std3, _ptr(out.params), _ptr(self._near),
+                                                  _ptr(out.image), _ptr(out.label), st), "cavp_aug_resize_render")
+        self._last = out
+        return out
+
     def __call__(self, frames: torch.Tensor, masks: torch.Tensor, sizes: torch.Tensor, params: Optional[torch.Tensor] = None,
                  out: Optional[AugResult] = None) -> AugResult:
         """params: int32 [B, 16] on the device, replaces the draws (PARAM_FIELDS; words 12..15 are ignored).
@@ -222,5 +275,6 @@ class FrameAugment:
     def eval_(self, frames: torch.Tensor, masks: torch.Tensor, sizes: torch.Tensor, out: Optional[AugResult] = None) -> AugResult:
         """The reference's test_aug (visual_aug.py:69-73): ToTensor + Normalize of the top-left H x W window, the mask widened to
         int64, through the render kernel with an identity plan (no draw is used, the offset still advances).  Where a staged
-        frame is smaller than the window the rest is pad_fill / 255."""
+        frame is smaller than the window the rest is pad_fill / 255.  With resize=True: every frame and mask resized to H x W
+        (BICUBIC / NEAREST) first, straight from the staged frames; needs stage_side <= 8 * crop_side."""
         return self._run(frames, masks, sizes, None, out, True)

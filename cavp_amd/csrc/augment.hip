@@ -14,6 +14,10 @@ constexpr int kAugTileH = 16, kAugTileW = 64;
 constexpr int kAugRows = 64;       // horizontally resampled rows a tile keeps in LDS: <= 15 * (in / out) + 2 * support + 2
 constexpr int kAugMaxScales = 16;
 constexpr int kAugParams = 16;     // int32 words of a sample's row of the parameter table
+// the resize variant's second pass (scaled image -> H x W): in / out <= kRzRatio on either axis
+constexpr int kRzRatio = 8;
+constexpr int kRzTaps = 34;        // <= 2 * 2 * kRzRatio + 2
+constexpr int kRzRows = 154;       // <= 15 * kRzRatio + 2 * 2 * kRzRatio + 2
 // the row of the parameter table (cavp_hip.h)
 enum { P_FLIP = 0, P_SCALE = 1, P_ORDER = 2, P_BRIGHT = 6, P_CONTRAST = 7, P_SAT = 8, P_HUE = 9, P_TOP = 10, P_LEFT = 11, P_SH = 12,
        P_SW = 13, P_MEAN = 14, P_FLAGS = 15 };
@@ -43,8 +47,28 @@ __device__ void aug_nearest_walk(int in, int out, int first, int count, bool mir
   }
 }
 
+// The resize variant's mask is NEAREST (scaled -> out) of NEAREST (in -> scaled): both walks are monotone, so the first is advanced
+// only as far as the second asks and no table of the scaled size exists.  tab[i] = source index of output index i, i in [0, out).
+__device__ void aug_nearest_walk2(int in, int scaled, int out, bool mirror, int* __restrict__ tab) {
+  const double a1 = (double)in / (double)scaled, a2 = (double)scaled / (double)out;
+  double x1 = a1 * 0.5, x2 = a2 * 0.5;
+  int at = 0;   // x1 is the accumulated sum of scaled index `at`
+  for (int i = 0; i < out; ++i) {
+    int s1 = (int)x2;
+    s1 = s1 < 0 ? 0 : s1 >= scaled ? scaled - 1 : s1;
+    for (; at < s1; ++at) x1 += a1;
+    int s = (int)x1;
+    s = s < 0 ? 0 : s >= in ? in - 1 : s;
+    tab[i] = mirror ? in - 1 - s : s;
+    x2 += a2;
+  }
+}
+
+// resize != 0: the reference's resize_flag variant - streams 0 .. 3 as below, no crop origin (stream 4 is not drawn, top = left = 0,
+// words 10, 11 of params_in are ignored), no pad and no crop: nothing is "too small", near_tab is the composed walk to H x W.
 __global__ __launch_bounds__(kAugMaxB) void aug_plan_kernel(const int* __restrict__ sizes, int B, int Hs, int Ws, int H, int W,
-                                                            AugScales sc, int jitter, int identity, const int* __restrict__ params_in,
+                                                            AugScales sc, int jitter, int identity, int resize,
+                                                            const int* __restrict__ params_in,
                                                             long long* __restrict__ state, int* __restrict__ params,
                                                             int* __restrict__ near_tab, unsigned long long* __restrict__ lsum) {
   __shared__ int s_bad;
@@ -107,8 +131,9 @@ __global__ __launch_bounds__(kAugMaxB) void aug_plan_kernel(const int* __restric
         const float hf = -0.25f + 0.5f * aug_u01((unsigned)(d3 >> 32));
         hue = ((int)(hf * 255.0f)) & 255;                 // torchvision: uint8(hue * 255), truncated, mod 256
       }
-      k4 = philox_key((unsigned)t, 4u, o0, o1, k0, k1);
+      if (!resize) k4 = philox_key((unsigned)t, 4u, o0, o1, k0, k1);
     }
+    if (resize) top = left = 0;
     // scaled size: int(h * s) with s = num / 64 is the exact integer floor(h * num / 64)
     const int num = identity ? 64 : sc.num[si];
     int sh = (int)(((long long)h * num) >> 6), sw = (int)(((long long)w * num) >> 6);
@@ -124,9 +149,11 @@ __global__ __launch_bounds__(kAugMaxB) void aug_plan_kernel(const int* __restric
       ph = sh + max(W - sh, 0);
     }
     if (identity) { ph = max(sh, H); pw = max(sw, W); }   // eval_: the top-left window, fill where the frame is smaller
+    if (resize) { ph = H; pw = W; }                      // no pad, no crop: the origin is (0, 0) by construction
     if (ph < H || pw < W) bad = 1;                       // RandomCrop.get_params raises here
     const int tmax = max(ph - H, 0), lmax = max(pw - W, 0);
-    if (!identity && !params_in) {
+    if (resize) {
+    } else if (!identity && !params_in) {
       top = aug_below((unsigned)(k4 >> 32), tmax + 1);
       left = aug_below((unsigned)k4, lmax + 1);
     } else if (top < 0 || top > tmax || left < 0 || left > lmax) {
@@ -141,8 +168,13 @@ __global__ __launch_bounds__(kAugMaxB) void aug_plan_kernel(const int* __restric
     q[P_HUE] = hue; q[P_TOP] = top; q[P_LEFT] = left; q[P_SH] = sh; q[P_SW] = sw; q[P_MEAN] = -1; q[P_FLAGS] = bad;
     lsum[t] = 0ull;
     int* tab = near_tab + (size_t)t * (H + W);
-    aug_nearest_walk(h, sh, top, H, false, tab);
-    aug_nearest_walk(w, sw, left, W, flip != 0, tab + H);
+    if (resize) {
+      aug_nearest_walk2(h, sh, H, false, tab);
+      aug_nearest_walk2(w, sw, W, flip != 0, tab + H);
+    } else {
+      aug_nearest_walk(h, sh, top, H, false, tab);
+      aug_nearest_walk(w, sw, left, W, flip != 0, tab + H);
+    }
     if (bad) atomicAdd(&s_bad, 1);
   }
   __syncthreads();
@@ -162,7 +194,9 @@ __device__ __forceinline__ double aug_bicubic(double x) {
 }
 
 // PIL's precompute_coeffs + normalize_coeffs_8bpc for output index i of an in -> out BICUBIC pass: first tap, tap count and
-// the taps at 22 fractional bits.  in == out gives the identity (one tap of 1 << 22).
+// the taps at 22 fractional bits.  in == out gives the identity (one tap of 1 << 22).  TAPS: the capacity of k (kAugTaps for the
+// scale pass, kRzTaps for the resize variant's second pass).
+template <int TAPS>
 __device__ void aug_coeffs(int in, int out, int i, int* __restrict__ first, int* __restrict__ count, int* __restrict__ k) {
   const double scale = (double)in / (double)out;
   const double fscale = scale < 1.0 ? 1.0 : scale;
@@ -173,15 +207,15 @@ __device__ void aug_coeffs(int in, int out, int i, int* __restrict__ first, int*
   int xmax = (int)(center + support + 0.5);
   if (xmax > in) xmax = in;
   int n = xmax - xmin;
-  if (n > kAugTaps) n = kAugTaps;
-  double w[kAugTaps], ww = 0.0;
+  if (n > TAPS) n = TAPS;
+  double w[TAPS], ww = 0.0;
 #pragma unroll
-  for (int x = 0; x < kAugTaps; ++x) {
+  for (int x = 0; x < TAPS; ++x) {
     w[x] = x < n ? aug_bicubic((x + xmin - center + 0.5) * ss) : 0.0;
     if (x < n) ww += w[x];
   }
 #pragma unroll
-  for (int x = 0; x < kAugTaps; ++x) {
+  for (int x = 0; x < TAPS; ++x) {
     double v = w[x];
     if (ww != 0.0) v = v / ww;
     v = v * 4194304.0;
@@ -213,13 +247,13 @@ __device__ unsigned aug_resize_tile(const unsigned char* __restrict__ frame, int
   if (t < kAugTileW) {
     const int x = x0 + t;
     int first = 0, count = 0;
-    if (x < sw) aug_coeffs(w, sw, x, &first, &count, L.hk[t]);
+    if (x < sw) aug_coeffs<kAugTaps>(w, sw, x, &first, &count, L.hk[t]);
     L.hmin[t] = first;
     L.hn[t] = count;
   } else if (t < kAugTileW + kAugTileH) {
     const int r = t - kAugTileW, y = y0 + r;
     int first = 0, count = 0;
-    if (y < sh) aug_coeffs(h, sh, y, &first, &count, L.vk[r]);
+    if (y < sh) aug_coeffs<kAugTaps>(h, sh, y, &first, &count, L.vk[r]);
     L.vmin[r] = first;
     L.vn[r] = count;
   }
@@ -445,6 +479,143 @@ __global__ __launch_bounds__(256) void aug_render_kernel(const unsigned char* __
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------- resize variant
+// The reference's resize_flag = True (dataset/avss/visual/visual_aug.py): flip, random scale, jitter, then a second BICUBIC /
+// NEAREST resize to H x W in place of pad + crop.  PIL rounds to uint8 between the two resizes and the contrast mean is over
+// the whole scaled image, so the scaled, flipped, jittered image is stored once (4 bytes per pixel) and resampled from there.
+
+// scratch [B][mh][mw] (r | g << 8 | b << 16): the tile at (16 blockIdx.y, 64 blockIdx.x) of sample blockIdx.z's scaled image
+__global__ __launch_bounds__(256) void aug_resize_store_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ sizes,
+                                                               int Hs, int Ws, int mh, int mw, int jitter, int* __restrict__ params,
+                                                               const unsigned long long* __restrict__ lsum,
+                                                               unsigned* __restrict__ scratch) {
+  __shared__ AugTileLds L;
+  const int b = blockIdx.z, t = threadIdx.x;
+  int* p = params + (size_t)b * kAugParams;
+  const int sh = min(p[P_SH], mh), sw = min(p[P_SW], mw);
+  const int y0 = blockIdx.y * kAugTileH, x0 = blockIdx.x * kAugTileW;
+  if (y0 >= sh || x0 >= sw) return;
+  const int h = min(max(sizes[2 * b], 1), Hs), w = min(max(sizes[2 * b + 1], 1), Ws);
+  int mean = 0;
+  if (jitter) {   // as in the render kernel of the crop variant
+    const unsigned long long n = (unsigned long long)p[P_SH] * (unsigned long long)p[P_SW];
+    mean = (int)((2ull * lsum[b] + n) / (2ull * n));
+    mean = mean > 255 ? 255 : mean;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) p[P_MEAN] = mean;
+  }
+  unsigned px[4];
+  const unsigned valid = aug_resize_tile(frames + (size_t)b * Hs * Ws * 3, Ws * 3, h, w, sh, sw, p[P_FLIP], y0, x0, L, px);
+  AugJitter j;
+  if (jitter) j = aug_load_jitter(p);
+  const int x = x0 + (t & 63);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = y0 + (t >> 6) + 4 * k;
+    if (valid & (1u << k)) scratch[((size_t)b * mh + y) * mw + x] = jitter ? aug_jitter_pixel(px[k], j, mean) : px[k];
+  }
+}
+
+struct AugResizeLds {
+  int hk[kAugTileW][kRzTaps + 1];   // (odd stride, as in AugTileLds)
+  int vk[kAugTileH][kRzTaps + 1];
+  int hmin[kAugTileW], hn[kAugTileW], vmin[kAugTileH], vn[kAugTileH];
+  unsigned rows[kRzRows][kAugTileW];
+};
+
+// One 16 x 64 tile of the H x W output per workgroup: two-pass BICUBIC from a source of per-sample size (ih, iw) - the scratch
+// of the store pass (SRC3 = false, 4 bytes per pixel) or, for eval_, the staged frame itself (SRC3 = true, 3 bytes per pixel) -
+// then /255, normalise, NCHW store; the mask through the plan kernel's composed nearest table.
+template <bool SRC3>
+__global__ __launch_bounds__(256) void aug_resize_render_kernel(const unsigned char* __restrict__ src, long long sample_bytes,
+                                                                int pitch_bytes, int cap_h, int cap_w,
+                                                                const unsigned char* __restrict__ masks, const int* __restrict__ sizes,
+                                                                int Hs, int Ws, int H, int W, AugNorm nm, const int* __restrict__ params,
+                                                                const int* __restrict__ near_tab, float* __restrict__ image,
+                                                                long long* __restrict__ label) {
+  __shared__ AugResizeLds L;
+  const int b = blockIdx.z, t = threadIdx.x;
+  const int* p = params + (size_t)b * kAugParams;
+  // the source's size: never beyond what the buffer holds
+  const int ih = SRC3 ? min(max(sizes[2 * b], 1), Hs) : min(max(p[P_SH], 1), cap_h);
+  const int iw = SRC3 ? min(max(sizes[2 * b + 1], 1), Ws) : min(max(p[P_SW], 1), cap_w);
+  const int y0 = blockIdx.y * kAugTileH, x0 = blockIdx.x * kAugTileW;
+  const unsigned char* img = src + (size_t)b * sample_bytes;
+  if (t < kAugTileW) {
+    int first = 0, count = 0;
+    if (x0 + t < W) aug_coeffs<kRzTaps>(iw, W, x0 + t, &first, &count, L.hk[t]);
+    L.hmin[t] = first;
+    L.hn[t] = count;
+  } else if (t < kAugTileW + kAugTileH) {
+    const int r = t - kAugTileW;
+    int first = 0, count = 0;
+    if (y0 + r < H) aug_coeffs<kRzTaps>(ih, H, y0 + r, &first, &count, L.vk[r]);
+    L.vmin[r] = first;
+    L.vn[r] = count;
+  }
+  __syncthreads();
+  const int ylast = min(kAugTileH - 1, H - 1 - y0);   // >= 0: the grid covers H
+  const int r0 = L.vmin[0];
+  int nrows = L.vmin[ylast] + L.vn[ylast] - r0;
+  nrows = nrows > kRzRows ? kRzRows : nrows;
+  for (int idx = t; idx < nrows * kAugTileW; idx += 256) {
+    const int rr = idx >> 6, x = idx & 63;
+    unsigned v = 0u;
+    if (x0 + x < W) {
+      const unsigned char* row = img + (size_t)min(r0 + rr, ih - 1) * pitch_bytes;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      const int first = L.hmin[x], n = L.hn[x];
+      for (int k = 0; k < n; ++k) {
+        const int sx = min(first + k, iw - 1);
+        const int c = L.hk[x][k];
+        if (SRC3) {
+          const unsigned char* q = row + 3 * sx;
+          a0 += q[0] * c;
+          a1 += q[1] * c;
+          a2 += q[2] * c;
+        } else {
+          const unsigned q = ((const unsigned*)row)[sx];
+          a0 += (int)(q & 255u) * c;
+          a1 += (int)((q >> 8) & 255u) * c;
+          a2 += (int)((q >> 16) & 255u) * c;
+        }
+      }
+      v = (unsigned)aug_clip8(a0) | ((unsigned)aug_clip8(a1) << 8) | ((unsigned)aug_clip8(a2) << 16);
+    }
+    L.rows[rr][x] = v;
+  }
+  __syncthreads();
+  const int x = t & 63, ox = x0 + x;
+  if (ox >= W) return;
+  const int* ytab = near_tab + (size_t)b * (H + W);
+  const int sx = ytab[H + ox];
+  const size_t plane = (size_t)H * W;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int y = (t >> 6) + 4 * j, oy = y0 + y;
+    if (y > ylast) continue;
+    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+    const int first = L.vmin[y] - r0, n = L.vn[y];
+    for (int k = 0; k < n; ++k) {
+      const unsigned v = L.rows[min(first + k, kRzRows - 1)][x];
+      const int c = L.vk[y][k];
+      a0 += (int)(v & 255u) * c;
+      a1 += (int)((v >> 8) & 255u) * c;
+      a2 += (int)((v >> 16) & 255u) * c;
+    }
+    const int px[3] = {aug_clip8(a0), aug_clip8(a1), aug_clip8(a2)};
+    float* o = image + (size_t)b * 3 * plane + (size_t)oy * W + ox;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float u = (float)px[c] / 255.0f;               // ToTensor
+      o[c * plane] = (u - nm.mean[c]) / nm.std[c];         // Normalize
+    }
+    const int sy = ytab[oy];
+    long long m = 255;
+    if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) m = (long long)masks[(size_t)b * Hs * Ws + (size_t)sy * Ws + sx];
+    label[(size_t)b * plane + (size_t)oy * W + ox] = m;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------ entry points
 static bool aug_shape_ok(int B, int Hs, int Ws, int H, int W) {
   return B >= 1 && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1;
@@ -453,12 +624,27 @@ static bool aug_shape_supported(int B, int Hs, int Ws, int H, int W) {
   return B <= kAugMaxB && Hs <= 16384 && Ws <= 16384 && H <= Hs && W <= Ws;
 }
 
-extern "C" int cavp_aug_plan(const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* scales64,
-                             int32_t n_scales, int32_t jitter, int32_t identity, const int32_t* params_in, int64_t* state,
-                             int32_t* params, int32_t* near_tab, uint64_t* lsum, void* stream) {
+// the resize variant: the output may be larger than the slot (an upscale), but the second pass holds at most kRzTaps taps, so the
+// largest scaled side may be at most kRzRatio times the output side
+static bool aug_resize_supported(int B, int Hs, int Ws, int H, int W, int max_scale64) {
+  if (B > kAugMaxB || Hs > 16384 || Ws > 16384 || H > 16384 || W > 16384 || max_scale64 < 32 || max_scale64 > 256) return false;
+  const long long mh = ((long long)Hs * max_scale64) >> 6, mw = ((long long)Ws * max_scale64) >> 6;
+  return mh <= (long long)kRzRatio * H && mw <= (long long)kRzRatio * W;
+}
+
+static int aug_plan_launch(const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* scales64,
+                           int32_t n_scales, int32_t jitter, int32_t identity, int resize, const int32_t* params_in, int64_t* state,
+                           int32_t* params, int32_t* near_tab, uint64_t* lsum, void* stream) {
   if (!sizes || !state || !params || !near_tab || !lsum || !aug_shape_ok(B, Hs, Ws, H, W)) return CAVP_ERR_BAD_ARG;
   if (!identity && (!scales64 || n_scales < 1)) return CAVP_ERR_BAD_ARG;
-  if (!aug_shape_supported(B, Hs, Ws, H, W) || n_scales > kAugMaxScales) return CAVP_ERR_UNSUPPORTED;
+  if (n_scales > kAugMaxScales) return CAVP_ERR_UNSUPPORTED;
+  if (resize) {
+    int mx = identity ? 64 : 0;
+    for (int i = 0; !identity && i < n_scales; ++i) mx = scales64[i] > mx ? scales64[i] : mx;
+    if (!aug_resize_supported(B, Hs, Ws, H, W, mx > 256 ? 256 : mx)) return CAVP_ERR_UNSUPPORTED;
+  } else if (!aug_shape_supported(B, Hs, Ws, H, W)) {
+    return CAVP_ERR_UNSUPPORTED;
+  }
   AugScales sc;
   sc.n = identity ? 1 : n_scales;
   for (int i = 0; i < kAugMaxScales; ++i) sc.num[i] = 64;
@@ -466,9 +652,22 @@ extern "C" int cavp_aug_plan(const int32_t* sizes, int32_t B, int32_t Hs, int32_
     if (scales64[i] < 32 || scales64[i] > 256) return CAVP_ERR_UNSUPPORTED;   // 0.5 .. 4: the tap and LDS row bounds above
     sc.num[i] = scales64[i];
   }
-  aug_plan_kernel<<<1, kAugMaxB, 0, (hipStream_t)stream>>>(sizes, B, Hs, Ws, H, W, sc, jitter ? 1 : 0, identity ? 1 : 0, params_in,
+  aug_plan_kernel<<<1, kAugMaxB, 0, (hipStream_t)stream>>>(sizes, B, Hs, Ws, H, W, sc, jitter ? 1 : 0, identity ? 1 : 0, resize, params_in,
                                                            (long long*)state, params, near_tab, (unsigned long long*)lsum);
   CHECK_LAUNCH();
+}
+
+extern "C" int cavp_aug_plan(const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* scales64,
+                             int32_t n_scales, int32_t jitter, int32_t identity, const int32_t* params_in, int64_t* state,
+                             int32_t* params, int32_t* near_tab, uint64_t* lsum, void* stream) {
+  return aug_plan_launch(sizes, B, Hs, Ws, H, W, scales64, n_scales, jitter, identity, 0, params_in, state, params, near_tab, lsum, stream);
+}
+
+extern "C" int cavp_aug_plan_resize(const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                                    const int32_t* scales64, int32_t n_scales, int32_t jitter, int32_t identity,
+                                    const int32_t* params_in, int64_t* state, int32_t* params, int32_t* near_tab, uint64_t* lsum,
+                                    void* stream) {
+  return aug_plan_launch(sizes, B, Hs, Ws, H, W, scales64, n_scales, jitter, identity, 1, params_in, state, params, near_tab, lsum, stream);
 }
 
 extern "C" int cavp_aug_contrast_mean(const uint8_t* frames, const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws,
@@ -500,5 +699,45 @@ extern "C" int cavp_aug_render(const uint8_t* frames, const uint8_t* masks, cons
   const dim3 grid((W + kAugTileW - 1) / kAugTileW, (H + kAugTileH - 1) / kAugTileH, B);
   aug_render_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(frames, masks, sizes, Hs, Ws, H, W, nm, jitter ? 1 : 0, params, near_tab,
                                                            (const unsigned long long*)lsum, image, (long long*)label);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_aug_resize_store(const uint8_t* frames, const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t max_scale64,
+                                     int32_t jitter, int32_t* params, const uint64_t* lsum, uint32_t* scratch, void* stream) {
+  if (!frames || !sizes || !params || !lsum || !scratch || B < 1 || Hs < 1 || Ws < 1) return CAVP_ERR_BAD_ARG;
+  if (B > kAugMaxB || Hs > 16384 || Ws > 16384 || max_scale64 < 32 || max_scale64 > 256) return CAVP_ERR_UNSUPPORTED;
+  const int mh = (int)(((long long)Hs * max_scale64) >> 6), mw = (int)(((long long)Ws * max_scale64) >> 6);
+  const dim3 grid((mw + kAugTileW - 1) / kAugTileW, (mh + kAugTileH - 1) / kAugTileH, B);
+  if (grid.y > 65535u) return CAVP_ERR_UNSUPPORTED;
+  aug_resize_store_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(frames, sizes, Hs, Ws, mh, mw, jitter ? 1 : 0, params,
+                                                                 (const unsigned long long*)lsum, scratch);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_aug_resize_render(const void* src, int32_t src_is_frames, const uint8_t* masks, const int32_t* sizes, int32_t B,
+                                      int32_t Hs, int32_t Ws, int32_t max_scale64, int32_t H, int32_t W, const float* mean3,
+                                      const float* std3, const int32_t* params, const int32_t* near_tab, float* image, int64_t* label,
+                                      void* stream) {
+  if (!src || !masks || !sizes || !mean3 || !std3 || !params || !near_tab || !image || !label || !aug_shape_ok(B, Hs, Ws, H, W))
+    return CAVP_ERR_BAD_ARG;
+  if (!aug_resize_supported(B, Hs, Ws, H, W, src_is_frames ? 64 : max_scale64)) return CAVP_ERR_UNSUPPORTED;
+  AugNorm nm;
+  for (int c = 0; c < 3; ++c) {   // HOST arrays, passed by value as in cavp_aug_render; the variant has no pad, so no fill
+    if (!(std3[c] > 0.0f)) return CAVP_ERR_BAD_ARG;
+    nm.mean[c] = mean3[c];
+    nm.std[c] = std3[c];
+    nm.fill[c] = 0;
+  }
+  const dim3 grid((W + kAugTileW - 1) / kAugTileW, (H + kAugTileH - 1) / kAugTileH, B);
+  if (grid.y > 65535u) return CAVP_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (src_is_frames) {
+    aug_resize_render_kernel<true><<<grid, 256, 0, s>>>((const unsigned char*)src, (long long)Hs * Ws * 3, Ws * 3, Hs, Ws, masks, sizes, Hs,
+                                                        Ws, H, W, nm, params, near_tab, image, (long long*)label);
+  } else {
+    const int mh = (int)(((long long)Hs * max_scale64) >> 6), mw = (int)(((long long)Ws * max_scale64) >> 6);
+    aug_resize_render_kernel<false><<<grid, 256, 0, s>>>((const unsigned char*)src, (long long)mh * mw * 4, mw * 4, mh, mw, masks, sizes,
+                                                         Hs, Ws, H, W, nm, params, near_tab, image, (long long*)label);
+  }
   CHECK_LAUNCH();
 }

@@ -719,6 +719,64 @@ int cavp_aug_render(const uint8_t* frames, const uint8_t* masks, const int32_t* 
                     int32_t W, const float* mean3, const float* std3, const int32_t* fill3, int32_t jitter, int32_t* params,
                     const int32_t* near_tab, const uint64_t* lsum, float* image, int64_t* label, void* stream);
 
+/* ---- Frame augmentation, resize variant (three entry points added to ABI 16; the three above are unchanged): the reference's
+ * resize_flag = True (dataset/avss/visual/visual_aug.py:31-35,71-72,81-82) - flip, random scale, jitter, then a second resize to
+ * H x W (BICUBIC frame, NEAREST mask) in place of pad + crop; PIL's arithmetic, restated in tests/_augment_resize_ref.py ----
+ * Launch order on one stream: plan_resize, contrast_mean (only with jitter; the entry point above, unchanged), resize_store,
+ * resize_render.  The test-time path (identity != 0: resize, ToTensor, Normalize) is plan_resize, resize_render on the frames.
+ * H x W may exceed the slot (an upscale).  The second pass holds 34 taps: floor(Hs * max_scale64 / 64) <= 8 H and the same for
+ * the widths (identity: Hs <= 8 H, Ws <= 8 W), CAVP_ERR_UNSUPPORTED otherwise.
+ * cavp_aug_plan_resize: the arguments, the params row and the draws of streams 0 .. 3 of the plan entry point above; stream 4 is not
+ *   drawn, top = left = 0 (words 10, 11 of params_in are ignored), no sample is "too small"; bad_inputs counts staged sizes outside
+ *   the slot, an empty scaled image and params_in fields out of range.  near_tab int32 [B][H + W]: the source row / column of every
+ *   output row / column through both NEAREST walks (scaled -> output, source -> scaled), mirrored under flip.
+ * cavp_aug_resize_store: scratch uint32 [B][mh][mw], mh = floor(Hs * max_scale64 / 64), mw likewise: the scaled, flipped, jittered
+ *   image r | g << 8 | b << 16 in the top-left sh x sw corner of the sample's slot (the two-pass BICUBIC of the crop variant,
+ *   rounded to uint8 after each pass); writes word 14 of the params row with jitter.
+ * cavp_aug_resize_render: the second two-pass BICUBIC from src - the scratch (src_is_frames == 0) or, for the test-time path, the
+ *   staged frames themselves (src_is_frames != 0, source size = sizes) - to image f32 [B][3][H][W] = ((u8 / 255) - mean) / std and
+ *   label int64 [B][H][W] through near_tab; one 16 x 64 output tile per workgroup, at most 154 horizontally resampled rows in LDS.
+ * No allocation, no synchronisation, no host read of a device value: the launches are capturable in a hipGraph. */
+int cavp_aug_plan_resize(const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* scales64,
+                         int32_t n_scales, int32_t jitter, int32_t identity, const int32_t* params_in, int64_t* state, int32_t* params,
+                         int32_t* near_tab, uint64_t* lsum, void* stream);
+int cavp_aug_resize_store(const uint8_t* frames, const int32_t* sizes, int32_t B, int32_t Hs, int32_t Ws, int32_t max_scale64,
+                          int32_t jitter, int32_t* params, const uint64_t* lsum, uint32_t* scratch, void* stream);
+int cavp_aug_resize_render(const void* src, int32_t src_is_frames, const uint8_t* masks, const int32_t* sizes, int32_t B, int32_t Hs,
+                           int32_t Ws, int32_t max_scale64, int32_t H, int32_t W, const float* mean3, const float* std3,
+                           const int32_t* params, const int32_t* near_tab, float* image, int64_t* label, void* stream);
+
+/* ---- Label stage (three entry points added to ABI 16; nothing else changed): the image labels the reference's data sets compute from
+ * the mask after the transform (vpo_mono/multi_source/visual/visual_dataset.py:127-145, avss/visual/visual_dataset.py:157-165,
+ * avsbench_ms.py:135-136), restated in tests/_labels_ref.py ----
+ * label: B images of HW pixels, contiguous, int64 (label_u8 == 0) or uint8 (label_u8 != 0); never written.  Launch order on one
+ * stream: presence (only with a remap), scan, expand.  B <= 1024, K <= 256.  16-byte loads when the base is 16-byte aligned and
+ * HW % 2 == 0 (int64) resp. HW % 16 == 0 (uint8), element loads otherwise.
+ *
+ * mask, raw_mask uint32 [B][8] (device, persistent): bit v of image b; both must be ZERO before the first call and are left zero by
+ *   the expand launch, so nothing is cleared outside the launches.
+ * presence: raw_mask[b] |= the values in [0, 256) of image b.
+ * scan, per pixel value v, in this order:
+ *   remap (int32 [256] on the device, optional): the reference's loop "for i in unique(label) without 0 and ignore, ascending:
+ *     label[label == i] = remap[i]" runs in place over a value list taken before the loop, so a pixel moved to t > i moves again at
+ *     step t when t was in the raw image.  Per pixel: x = v; t = remap[x]; while t > x, t in the raw image, t not 0 and not ignore:
+ *     x = t, t = remap[x]; the result is t.  remap[x] outside [0, 255] (-1 = "the reference raises"): the pixel keeps x and is bad.
+ *     A v outside [0, 256) is no key of the table: it is kept and is bad unless it equals ignore.
+ *   class bit, any_foreground == 0: mask[b] bit f for the result f in [0, K) and != ignore; f outside [0, K) and != ignore: bad, no bit.
+ *              any_foreground != 0 (K == 2): bit 1 for every f != 0 (ignore included, as in the reference's sum).
+ *   binary != 0: f != 0 and f != ignore becomes 1 (after the class bit, as in the AVSS data set).
+ *   out_label int64 [B][HW] (optional): the value after these steps.  state int64[4] (device, persistent): state[0] += the pixels
+ *   that were bad by at least one rule; no value makes a kernel read or write out of bounds.
+ * expand: img_label int64 [B][K] = the bits (any_foreground: {1, 0} without bit 1, {0, 1} with it); clears mask and raw_mask (NULL
+ *   without a remap).
+ * No allocation, no synchronisation, no host read of a device value: the launches are capturable in a hipGraph. */
+int cavp_labels_presence(const void* label, int32_t label_u8, int32_t B, int64_t HW, uint32_t* raw_mask, void* stream);
+int cavp_labels_scan(const void* label, int32_t label_u8, int32_t B, int64_t HW, int32_t K, int32_t any_foreground,
+                     const int32_t* remap, int32_t binary, int64_t ignore, const uint32_t* raw_mask, uint32_t* mask, int64_t* state,
+                     int64_t* out_label, void* stream);
+int cavp_labels_expand(uint32_t* mask, uint32_t* raw_mask, int32_t B, int32_t K, int32_t any_foreground, int64_t* img_label,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

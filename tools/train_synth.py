@@ -11,7 +11,7 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
-                                   [--contrast [--contrast-weight W]] [--pairs] [--graph]
+                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize]]]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -24,6 +24,12 @@ ContrastLoss with the device sampler on the fusion map; the shuffle labels are t
 backward and the optimiser step with the learning-rate schedule on the device (FusedSGDAdam.use_device_schedule,
 CAVP.capture_train_step(optimizer=, prologue=)).  Two captures share the optimiser's device state: one without the sound-bank
 overwrite for step 0, one with it for the rest.  The loop is "copy the batch into the static buffers, replay".
+
+--augment (with --graph): the batch is raw material - synthetic uint8 frames and masks with a few class blobs in raw (data-set)
+class indices - and the captured prologue is the whole input chain FrameAugment -> LabelStage -> PairBuilder -> MelFrontEnd: the
+image labels the pair builder sees are computed on the device from the augmented, remapped mask, as the reference's data sets
+compute them after their transform.  --resize: the AVSS set-ups' variant (the AVS scale list, no jitter, a resize to --hw instead
+of pad + crop).
 """
 import argparse
 import os
@@ -59,7 +65,13 @@ def main():
     ap.add_argument("--pairs", action="store_true", help="build the shuffled half of the batch and its labels with PairBuilder")
     ap.add_argument("--ow-rate", type=float, default=0.5, help="share of the mismatched rows overwritten from the sound bank")
     ap.add_argument("--graph", action="store_true", help="one hipGraph per iteration: pairs, log-mel, step and optimiser (device schedule)")
+    ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
+    ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
     a = ap.parse_args()
+    if a.augment and not a.graph:
+        ap.error("--augment needs --graph (with --from-waveform --contrast --pairs)")
+    if a.resize and not a.augment:
+        ap.error("--resize needs --augment")
     if a.pairs and not (a.from_waveform and a.contrast):
         ap.error("--pairs needs --from-waveform and --contrast")
     if a.graph and not a.pairs:
@@ -117,7 +129,21 @@ def main():
         img_label[:, 0] = torch.randint(0, 2, (B,), generator=g)
         return wave, img_label
 
+    RAW0 = 10          # --augment: the raw mask holds RAW0 + c where the model's class is c (a data set's own index space)
+
+    def draw_raw_batch(stage):
+        """B raw frames and masks (host uint8): noise with one or two rectangular blobs of a foreground class each"""
+        frames = torch.randint(0, 256, (B,) + stage + (3,), dtype=torch.uint8, generator=g)
+        masks = torch.zeros((B,) + stage, dtype=torch.uint8)
+        for b in range(B):
+            for _ in range(1 + int(torch.rand((), generator=g) < 0.25)):
+                c = int(torch.randint(1, pairs.K, (), generator=g))
+                y, x = (int(torch.randint(0, stage[k] // 2, (), generator=g)) for k in (0, 1))
+                masks[b, y:y + stage[0] // 3, x:x + stage[1] // 3] = RAW0 + c
+        return frames, masks
+
     replays = None
+    aug = None
     if a.graph:
         from cavp_amd.pairs import PairResult
         s_image = torch.zeros(B, 3, a.hw, a.hw, device=dev)
@@ -132,8 +158,28 @@ def main():
         opt.use_device_schedule(a.lr, a.lr_power, a.total_iters, 0)
         start = {k: v.clone() for k, v in model.state_dict().items()}
 
+        if a.augment:
+            from cavp_amd.augment import AVS_SCALES, COCO_SCALES, AugResult, FrameAugment
+            from cavp_amd.labels import LabelResult, LabelStage
+            stage = (a.hw + a.hw // 2,) * 2
+            aug = FrameAugment(crop=(a.hw, a.hw), scales=AVS_SCALES if a.resize else COCO_SCALES, jitter=None if a.resize else (.5, .5, .5, .25),
+                               seed=1234 + rank, device=dev, max_batch=B, stage=stage, resize=a.resize)
+            remap = torch.full((256,), -1, dtype=torch.int32)
+            remap[RAW0 + 1:RAW0 + pairs.K] = torch.arange(1, pairs.K, dtype=torch.int32)
+            stage_labels = LabelStage(num_classes=pairs.K, mode="multi_hot", remap=remap, device=dev, max_batch=B)
+            s_frames = torch.zeros((B,) + stage + (3,), dtype=torch.uint8, device=dev)
+            s_masks = torch.zeros((B,) + stage, dtype=torch.uint8, device=dev)
+            s_sizes = torch.tensor([list(stage)] * B, dtype=torch.int32, device=dev)
+            augmented, labelled = AugResult(B, (a.hw, a.hw), dev), LabelResult(B, pairs.K, (a.hw, a.hw), dev, True)
+
         def prologue_of(overwrite):
             def prologue():
+                if aug is not None:        # raw frames -> image, label -> remapped label, img_label: nothing returns to the host
+                    aug(s_frames, s_masks, s_sizes, out=augmented)
+                    stage_labels(augmented.label, out=labelled)
+                    s_image.copy_(augmented.image)
+                    s_label.copy_(labelled.label)
+                    s_img_label.copy_(labelled.img_label)
                 pairs(s_wave, s_label, s_img_label, overwrite, out=built)
                 s_audio.copy_(front(built.waveforms))
                 s_shuf.copy_(built.label_shuffle)
@@ -145,6 +191,8 @@ def main():
             replays.append((rep, model._last_losses))           # (each graph has its own static loss buffers)
         # the warm-up passes of the captures ran the pair builder, the sampler and the BatchNorm statistics for real: start over
         model.load_state_dict(start)
+        if aug is not None:
+            aug.manual_seed(1234 + rank)
         pairs.manual_seed(1234 + rank)
         pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
         crit.manual_seed(1234 + rank)
@@ -156,8 +204,13 @@ def main():
         label = torch.randint(0, a.num_classes, (B, a.hw, a.hw), generator=g)
         if replays is not None:                                 # copy the batch in, replay: nothing else is launched from here
             wave, img_label = draw_pairs_batch()
-            for dst, src in ((s_image, image), (s_label, label), (s_wave, wave), (s_img_label, img_label)):
-                dst.copy_(src)
+            if aug is not None:                                 # raw material only: image, label and img_label come from the prologue
+                frames, masks = draw_raw_batch(tuple(s_masks.shape[1:]))
+                for dst, src in ((s_frames, frames), (s_masks, masks), (s_wave, wave)):
+                    dst.copy_(src)
+            else:
+                for dst, src in ((s_image, image), (s_label, label), (s_wave, wave), (s_img_label, img_label)):
+                    dst.copy_(src)
             rep, graph_terms = replays[1 if it >= 1 else 0]
             loss = rep()
             if it == 1:
@@ -211,6 +264,11 @@ def main():
         plan = pairs.last_plan()
         print(f"pairs, last step: {int(plan['if_match'].sum())} of {B} rows matched, {plan['n_overwritten']} taken from the sound bank "
               f"(q = {plan['q']} of {plan['n_false']} mismatched), {plan['n_written']} clips queued")
+    if rank == 0 and aug is not None:
+        aug.check()
+        stage_labels.check()
+        print(f"input chain: {'resize' if a.resize else 'pad + crop'} augmentation, img_label from the augmented mask: "
+              f"{labelled.img_label[:, 1:].sum(0).tolist()} frames per foreground class in the last batch")
     if rank == 0 and a.fixed_batch:
         print(f"fixed batch: loss {first:.4f} -> {float(loss.item()):.4f} after {a.steps} steps")
     if world > 1:
