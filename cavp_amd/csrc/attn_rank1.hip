@@ -78,7 +78,7 @@ __device__ __forceinline__ float wave_total(float v) {
 }
 
 // 1 / (1 + e^-s) on the hardware exp2 / rcp (|relative error| ~ 1e-6: below the f32 accumulation noise of the 304-term dot product)
-__device__ __forceinline__ float sigmoidf_(float s) { return __frcp_rn(1.f + __expf(-s)); }
+__device__ __forceinline__ float sigmoidf_(float s) { return fast_rcp(1.f + fast_exp(-s)); }
 
 // u[b,h,i] = scale * sum_j Wq[h d + j, i] k[b, h d + j];  p[b,h,o] = sum_j Wp[o, h d + j] v[b, h d + j].  One workgroup per (b, h).
 template <typename T>

@@ -106,14 +106,26 @@ __device__ __forceinline__ float gelu_grad(float x) {  // d/dx [0.5 x (1 + erf(x
   return cdf + x * pdf;
 }
 
+// 1 / x as the hardware v_rcp_f32 (1 ulp) and exp(x) as v_exp_f32 of x * log2(e) without the denormal-range rescue, for formulas
+// that are approximations already.  __frcp_rn is NOT one instruction: it compiles to the correctly rounded IEEE division (2 x
+// v_div_scale, v_rcp, four FMAs of refinement, v_div_fmas, v_div_fixup: ~10 VALU), and __expf wraps v_exp_f32 in a compare /
+// select / rescale (~5 VALU) so that results below 2^-126 come out as denormals.  fast_exp flushes those to 0: use it where a
+// flushed result is the wanted one - the GELU's exp(-x^2 / 2), whose tiny results are rounded away anyway, and the attention gate's
+// 1 / (1 + exp(-s)) with s of either sign: a flushed exponential gives 1, an overflowed one inf and fast_rcp(inf) = 0, the limits.
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+
 // gelu(x) and gelu'(x) together, for the fused fc1 + GELU epilogue (cavp_conv_desc.aux_mode 1), where this math is NOT hidden
 // behind memory traffic: two erff + one expf per element (~70 VALU) made the fused epilogue cost what the two elementwise
 // passes it replaces had cost.  One exp(-x^2/2) serves the density AND the Abramowitz-Stegun 7.1.26 form of erf
-// (|error| <= 1.5e-7, below bf16 and f32-accumulation noise): ~18 VALU per element.
+// (|error| <= 1.5e-7, below bf16 and f32-accumulation noise).  With __expf / __frcp_rn this compiled to 30 VALU per element
+// (not the ~18 an earlier version of this comment claimed); with the hardware reciprocal and exponential (1 ulp each) it is
+// 20; measured in f32 against float64 on a grid over [-10, 10]: 3.7e-7 for g, 2.4e-7 for dg, the figures of the earlier form
+// (tests/test_gpu_gelu_epilogue_math.py holds them to 5e-7 for |x| <= 6).
 __device__ __forceinline__ void gelu_and_grad(float x, float& g, float& dg) {
   const float ax = fabsf(x);
-  const float e = __expf(-0.5f * x * x);                       // exp(-z^2), z = |x| / sqrt 2
-  const float t = __frcp_rn(fmaf(0.3275911f * 0.70710678118654752f, ax, 1.f));
+  const float e = fast_exp(-0.5f * x * x);                     // exp(-z^2), z = |x| / sqrt 2; 0 for |x| > 13.2 (the wanted limit)
+  const float t = fast_rcp(fmaf(0.3275911f * 0.70710678118654752f, ax, 1.f));
   float poly = fmaf(1.061405429f, t, -1.453152027f);
   poly = fmaf(poly, t, 1.421413741f);
   poly = fmaf(poly, t, -0.284496736f);
@@ -124,13 +136,13 @@ __device__ __forceinline__ void gelu_and_grad(float x, float& g, float& dg) {
   dg = fmaf(x * e, 0.3989422804014327f, cdf);
 }
 
-// gelu(x) alone in gelu_and_grad's form (one exp, one reciprocal, |error of the CDF| <= 1.5e-7: three orders of magnitude below the bf16
+// gelu(x) alone in gelu_and_grad's form (one exp, one reciprocal, error of the CDF a few 1e-7: three orders of magnitude below the bf16
 // rounding of the stored result).  The bf16 inference epilogues use it: with erff the 304 -> 1216 token linear of the eval forward ran
 // 252 us against 138 us for its 1216 -> 304 partner (profiles/r06_layers_eval_bf16.txt rows 90 / 91); the f32 parity path keeps erff.
 __device__ __forceinline__ float gelu_fast(float x) {
   const float ax = fabsf(x);
-  const float e = __expf(-0.5f * x * x);
-  const float t = __frcp_rn(fmaf(0.3275911f * 0.70710678118654752f, ax, 1.f));
+  const float e = fast_exp(-0.5f * x * x);
+  const float t = fast_rcp(fmaf(0.3275911f * 0.70710678118654752f, ax, 1.f));
   float poly = fmaf(1.061405429f, t, -1.453152027f);
   poly = fmaf(poly, t, 1.421413741f);
   poly = fmaf(poly, t, -0.284496736f);

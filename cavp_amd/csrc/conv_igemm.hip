@@ -168,7 +168,7 @@ __global__ __launch_bounds__(64 * WC * WP, (WC * WP == 4 ? (BC * BP <= 64 * 64 &
     int ti = g_ti < p.ntaps ? g_ti : p.ntaps - 1;
     if constexpr (UP) {
       if (p.up_par) {   // the class's own tap list (4 bits per launch tap index)
-        const int nt = p.par_nt[pq], gi = g_ti < nt ? g_ti : nt - 1;
+        const int nt = p.par_nt[pq], gi = g_ti < nt ? g_ti : (nt > 0 ? nt - 1 : 0);   // (a class with no live tap: nt == 0)
         ti = (int)((p.par_taps[pq] >> (4 * gi)) & 15ull);
       }
     }
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(64 * WC * WP, (WC * WP == 4 ? (BC * BP <= 64 * 64 &
       const int pix = p_base + row;
       const bool ok = (row < BP) && (pix < p.M);
       const int pp = ok ? pix : 0;
-      int n, ho, wo;
+      int n = 0, ho = 0, wo = 0;
       bool rok = ok;
       if (UP && p.up_par) {
         rok = ok && par_out_pixel(p, pp, n, ho, wo) >= 0;   // (padding slots of a class are dead rows)
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(64 * WC * WP, (WC * WP == 4 ? (BC * BP <= 64 * 64 &
         if (lrow == 0) {
           // (one reciprocal per wave and tile instead of an IEEE division per channel: this block is VALU time in front of every
           // store of a store-bound layer, profiles/r06_skinny_epilogue_anatomy.txt)
-          const float inv_n = __frcp_rn((float)(nvw < TP ? (nvw > 0 ? nvw : 1) : TP));
+          const float inv_n = fast_rcp((float)(nvw < TP ? (nvw > 0 ? nvw : 1) : TP));
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float m = s1[i] * inv_n;
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(64 * WC * WP, (WC * WP == 4 ? (BC * BP <= 64 * 64 &
         nb = nb < TP ? nb : TP;
         if (nb > 0) {
           const float2 q = wstat[w * BC + tid];
-          const float fb = (float)nb, nt = n + fb, dlt = q.x - mean, fr = fb * __frcp_rn(nt);   // (one reciprocal instead of two divisions)
+          const float fb = (float)nb, nt = n + fb, dlt = q.x - mean, fr = fb * fast_rcp(nt);   // (one reciprocal instead of two divisions)
           mean += dlt * fr;
           m2 += q.y + dlt * dlt * (n * fr);
           n = nt;

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(512, 2) void igemm_big_kernel(const IgemmParams p) 
         }
         const int c = c_wave + a * 16 + lgrp * 4;
         if (lrow == 0 && nvw > 0 && c < p.Cout) {
-          const float inv_n = __frcp_rn((float)(nvw < 128 ? nvw : 128));
+          const float inv_n = fast_rcp((float)(nvw < 128 ? nvw : 128));
           float4 o;
           float m = s1[0] * inv_n; o.x = x0[0] + m; o.y = fmaxf(s2[0] - s1[0] * m, 0.f);
           m = s1[1] * inv_n; o.z = x0[1] + m; o.w = fmaxf(s2[1] - s1[1] * m, 0.f);
