@@ -181,6 +181,9 @@ PROTOTYPES = {
     "cavp_labels_presence": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp]),
     "cavp_labels_scan": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "cavp_labels_expand": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    # ---- clip validation: frames routed into the ALL and the multi-source confusion matrix (added to ABI 16) ----
+    "cavp_clipval_frame_counts": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "cavp_clipval_combine": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -15,6 +15,8 @@
 //   mask_iou_stats: per image  sum p*t, sum max(p, t), sum (1-t)(1-p), sum t  in int64.
 //   fmeasure_hist:  per image a (pr_num+1)-bin histogram of bin(p) = #{i : th[i] <= p} over all pixels and over gt != 0;
 //                  suffix sums of it are Eval_Fmeasure's y_temp.sum() and tp for every threshold.
+//   clipval:       the frames of a batch of clips routed into an ALL and a multi-source confusion matrix: per frame a 256-bin label
+//                  histogram and the seg_confusion counts in scratch, then a flag per frame from its histogram and the adds.
 #include "common.h"
 #include "host_util.h"
 
@@ -28,8 +30,8 @@ __device__ __forceinline__ void argmax_step(float v, int c, float& best, int& id
 }
 
 // Add the (bin, count) pairs of one thread's 4 pixels (bin < 0: nothing).  Wave-uniform call.
-template <bool kLds>
-__device__ __forceinline__ void add_bins(int b[4], unsigned* lds, unsigned long long* gM) {
+template <bool kLds, typename G>
+__device__ __forceinline__ void add_bins(int b[4], unsigned* lds, G* gM) {
   int cnt[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) cnt[i] = b[i] >= 0 ? 1 : 0;
@@ -54,14 +56,14 @@ __device__ __forceinline__ void add_bins(int b[4], unsigned* lds, unsigned long 
                            4u * (unsigned)__popcll(__ballot(c & 4));
     if ((threadIdx.x & 63) == 0) {
       if (kLds) atomicAdd(lds + lead, total);
-      else atomicAdd(gM + lead, (unsigned long long)total);
+      else atomicAdd(gM + lead, (G)total);
     }
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     if (b[i] >= 0) {
       if (kLds) atomicAdd(lds + b[i], (unsigned)cnt[i]);
-      else atomicAdd(gM + b[i], (unsigned long long)cnt[i]);
+      else atomicAdd(gM + b[i], (G)cnt[i]);
     }
   }
 }
@@ -417,6 +419,175 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(const T* __restri
   }
 }
 
+// ---- clip validation: the frames of a batch of clips routed into the ALL and the multi-source (MS) matrix ------------------------
+// frame_kernel: per participating frame the 256-bin label histogram and the (K+1) x K confusion counts, as u32 in per-frame scratch.
+// flags_kernel: the frame's MS flag from its histogram (cleared again here), the frame counters, the bad `count` entries.
+// combine_kernel: the frames' confusion counts added into ALL / MS by their flags (scratch cleared again).
+constexpr int kLabelBins = 256;
+constexpr int kCombineFrames = 16;   // frames per combine workgroup
+
+// count[b] clamped to [0, T]; no count: every frame
+__device__ __forceinline__ long long clip_count_raw(const void* count, int count_i64, int b) {
+  return count_i64 ? ((const long long*)count)[b] : (long long)((const int*)count)[b];
+}
+__device__ __forceinline__ int clip_count(const void* count, int count_i64, int b, int T) {
+  if (!count) return T;
+  const long long c = clip_count_raw(count, count_i64, b);
+  return (int)(c < 0 ? 0 : (c > T ? T : c));
+}
+
+// grid (chunks, B*T): a workgroup belongs to one frame.  One thread = 4 consecutive pixels; block-uniform trip count (add_bins
+// ballots).  LDS: [256] label histogram, then (kLds) the frame's (K+1)*K confusion counts.  Every index is guarded before use: the
+// histogram bin by v < 256 (v < 0 takes `ignore`, which the host checks to be in [0, 256)), the confusion bin by p < K.
+template <bool kMask, bool kVec, bool kLds>
+__global__ __launch_bounds__(kThreads) void clipval_frame_kernel(const void* __restrict__ pred, const long long* __restrict__ labels,
+                                                                const void* __restrict__ count, int count_i64, int T, int C,
+                                                                long long HW, int K, int ignore, unsigned* __restrict__ hist,
+                                                                unsigned* __restrict__ conf, unsigned long long* __restrict__ state) {
+  extern __shared__ unsigned lds[];
+  const int n = blockIdx.y, b = n / T, t = n - b * T;
+  if (t >= clip_count(count, count_i64, b, T)) return;   // workgroup-uniform: the frame is not read
+  const int nbins = (K + 1) * K;
+  unsigned* lconf = lds + kLabelBins;
+  for (int i = threadIdx.x; i < kLabelBins + (kLds ? nbins : 0); i += kThreads) lds[i] = 0u;
+  __syncthreads();
+  unsigned* gconf = conf + (size_t)n * nbins;
+  const long long* lab_n = labels + (long long)n * HW;
+  const long long nq = (HW + 3) >> 2;
+  unsigned bad_label = 0, bad_mask = 0;
+  for (long long base = (long long)blockIdx.x * kThreads; base < nq; base += (long long)gridDim.x * kThreads) {
+    const long long q = base + threadIdx.x;
+    int hb[4] = {-1, -1, -1, -1}, cb[4] = {-1, -1, -1, -1};
+    if (q < nq) {
+      const long long p0 = q * 4;
+      const int np = kVec ? 4 : (int)(HW - p0 < 4 ? HW - p0 : 4);
+      const long long* lab = lab_n + p0;
+      long long tv[4] = {0, 0, 0, 0};
+      int p[4] = {0, 0, 0, 0};
+      if (kVec) {
+        const longlong2 t01 = *(const longlong2*)lab, t23 = *(const longlong2*)(lab + 2);
+        tv[0] = t01.x; tv[1] = t01.y; tv[2] = t23.x; tv[3] = t23.y;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j < np) tv[j] = lab[j];
+        }
+      }
+      if (kMask) {
+        const unsigned char* src = (const unsigned char*)pred + (long long)n * HW + p0;
+        if (kVec) {
+          const unsigned w = *(const unsigned*)src;
+          p[0] = w & 255u; p[1] = (w >> 8) & 255u; p[2] = (w >> 16) & 255u; p[3] = w >> 24;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (j < np) p[j] = src[j];
+          }
+        }
+      } else {
+        const float* src = (const float*)pred + (long long)n * C * HW + p0;
+        if (kVec) {
+          float4 best = *(const float4*)src;
+          for (int c = 1; c < C; ++c) {
+            const float4 v = *(const float4*)(src + c * HW);
+            argmax_step(v.x, c, best.x, p[0]);
+            argmax_step(v.y, c, best.y, p[1]);
+            argmax_step(v.z, c, best.z, p[2]);
+            argmax_step(v.w, c, best.w, p[3]);
+          }
+        } else {
+          float best[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) best[j] = j < np ? src[j] : 0.f;
+          for (int c = 1; c < C; ++c) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if (j < np) argmax_step(src[c * HW + j], c, best[j], p[j]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j >= np) continue;
+        const long long v = tv[j];
+        if (v >= kLabelBins) { ++bad_label; continue; }
+        if (kMask && p[j] >= K) { ++bad_mask; continue; }
+        hb[j] = v < 0 ? ignore : (int)v;
+        if (v >= 0 && v != ignore) cb[j] = (v < K ? (int)v : K) * K + p[j];
+      }
+    }
+    add_bins<true>(hb, lds, (unsigned*)nullptr);
+    add_bins<kLds>(cb, lconf, gconf);
+  }
+  if (bad_label) atomicAdd(state, (unsigned long long)bad_label);
+  if (bad_mask) atomicAdd(state + 1, (unsigned long long)bad_mask);
+  __syncthreads();
+  unsigned* ghist = hist + (size_t)n * kLabelBins;
+  for (int i = threadIdx.x; i < kLabelBins + (kLds ? nbins : 0); i += kThreads) {
+    const unsigned v = lds[i];
+    if (v) atomicAdd(i < kLabelBins ? ghist + i : gconf + (i - kLabelBins), v);
+  }
+}
+
+// grid B*T, 256 threads = the 256 histogram bins of one frame.  flags[n]: 0 = takes no part, 1 = ALL, 3 = ALL and MS.
+__global__ __launch_bounds__(kLabelBins) void clipval_flags_kernel(unsigned* __restrict__ hist, unsigned* __restrict__ flags,
+                                                                  const void* __restrict__ count, int count_i64, int T,
+                                                                  unsigned min_count, int min_values,
+                                                                  unsigned long long* __restrict__ frames,
+                                                                  unsigned long long* __restrict__ state) {
+  __shared__ int part[kLabelBins / 64];
+  const int n = blockIdx.x, b = n / T, t = n - b * T;
+  if (t == 0 && threadIdx.x == 0 && count) {
+    const long long c = clip_count_raw(count, count_i64, b);
+    if (c < 0 || c > T) atomicAdd(state + 2, 1ull);
+  }
+  if (t >= clip_count(count, count_i64, b, T)) {   // workgroup-uniform
+    if (threadIdx.x == 0) flags[n] = 0u;
+    return;
+  }
+  unsigned* h = hist + (size_t)n * kLabelBins + threadIdx.x;
+  const unsigned v = *h;
+  if (v) *h = 0u;
+  const int q = __popcll(__ballot(v > min_count));
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = q;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int values = 0;
+#pragma unroll
+    for (int w = 0; w < kLabelBins / 64; ++w) values += part[w];
+    const bool ms = values > min_values;
+    flags[n] = ms ? 3u : 1u;
+    atomicAdd(frames, 1ull);
+    if (ms) atomicAdd(frames + 1, 1ull);
+  }
+}
+
+// grid (ceil(nbins / 256), ceil(N / kCombineFrames)): one thread = one bin of kCombineFrames frames
+__global__ __launch_bounds__(kThreads) void clipval_combine_kernel(unsigned* __restrict__ conf, const unsigned* __restrict__ flags, int N,
+                                                                  int nbins, unsigned long long* __restrict__ counts) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= nbins) return;
+  const int n0 = blockIdx.y * kCombineFrames;
+  unsigned v[kCombineFrames], f[kCombineFrames];
+#pragma unroll
+  for (int k = 0; k < kCombineFrames; ++k) {
+    f[k] = n0 + k < N ? flags[n0 + k] : 0u;
+    v[k] = f[k] ? conf[(size_t)(n0 + k) * nbins + i] : 0u;
+  }
+  unsigned long long all = 0, ms = 0;
+#pragma unroll
+  for (int k = 0; k < kCombineFrames; ++k) {
+    if (v[k]) {
+      conf[(size_t)(n0 + k) * nbins + i] = 0u;
+      all += v[k];
+      if (f[k] & 2u) ms += v[k];
+    }
+  }
+  if (all) atomicAdd(counts + i, all);
+  if (ms) atomicAdd(counts + nbins + i, ms);
+}
+
 }  // namespace
 
 template <typename LT>
@@ -524,5 +695,73 @@ extern "C" int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, co
   hipStream_t s = (hipStream_t)stream;
   if (gi) fmeasure_hist_kernel<long long><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const long long*)gt, thresholds, C, channel, HW, pr_num, hist);
   else fmeasure_hist_kernel<float><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const float*)gt, thresholds, C, channel, HW, pr_num, hist);
+  CHECK_LAUNCH();
+}
+
+template <bool kMask>
+void launch_clipval_frames(bool vec, bool lds, dim3 grid, size_t shm, hipStream_t s, const void* pred, const long long* labels,
+                           const void* count, int count_i64, int T, int C, long long HW, int K, int ignore, unsigned* hist, unsigned* conf,
+                           unsigned long long* state) {
+#define CAVP_CLIPVAL(V, L)                                                                                                         \
+  do {                                                                                                                             \
+    static bool attr_set = false; /* K = 127: 64 KiB of counts + the 1 KiB histogram, past the 64 KiB default */                    \
+    if (!attr_set) {                                                                                                               \
+      (void)hipFuncSetAttribute((const void*)clipval_frame_kernel<kMask, V, L>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
+                                (kLdsBins + kLabelBins) * (int)sizeof(unsigned));                                                   \
+      attr_set = true;                                                                                                             \
+    }                                                                                                                              \
+    clipval_frame_kernel<kMask, V, L><<<grid, kThreads, shm, s>>>(pred, labels, count, count_i64, T, C, HW, K, ignore, hist, conf, \
+                                                                   state);                                                         \
+  } while (0)
+  if (vec && lds) CAVP_CLIPVAL(true, true);
+  else if (vec) CAVP_CLIPVAL(true, false);
+  else if (lds) CAVP_CLIPVAL(false, true);
+  else CAVP_CLIPVAL(false, false);
+#undef CAVP_CLIPVAL
+}
+
+static bool clipval_count_ok(const void* count, int32_t count_i64) { return !count || !((uintptr_t)count & (count_i64 ? 7 : 3)); }
+
+extern "C" int cavp_clipval_frame_counts(const void* pred, int32_t pred_is_mask, const int64_t* labels, const void* count,
+                                         int32_t count_i64, int32_t B, int32_t T, int32_t C, int64_t HW, int32_t K, int64_t ignore,
+                                         uint32_t* hist, uint32_t* conf, int64_t* state, void* stream) {
+  if (!pred || !labels || !hist || !conf || !state || B <= 0 || T <= 0 || HW <= 0 || K <= 0 || (!pred_is_mask && C <= 0))
+    return CAVP_ERR_BAD_ARG;
+  if (ignore < 0 || ignore >= kLabelBins) return CAVP_ERR_BAD_ARG;
+  if ((long long)B * T > 65535 || HW > 0x7fffffffLL) return CAVP_ERR_UNSUPPORTED;   // grid.y; u32 counts per frame
+  if (K > CAVP_METRICS_MAX_CLASSES || (!pred_is_mask && K < C)) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)labels & 7) || ((uintptr_t)hist & 3) || ((uintptr_t)conf & 3) || ((uintptr_t)state & 7) ||
+      (!pred_is_mask && ((uintptr_t)pred & 3)) || !clipval_count_ok(count, count_i64))
+    return CAVP_ERR_ALIGN;
+  const bool vec = (HW & 3) == 0 && al16(labels) && (pred_is_mask ? ((uintptr_t)pred & 3) == 0 : al16(pred));
+  const bool lds = (K + 1) * K <= kLdsBins;
+  // 2 quads per thread (25 workgroups per frame at 224^2): enough workgroups for a single clip, few enough LDS clears and flushes
+  const dim3 grid(chunks_for((HW + 3) >> 2, 2 * kThreads, 64), B * T);
+  const size_t shm = (size_t)(kLabelBins + (lds ? (K + 1) * K : 0)) * sizeof(unsigned);
+  hipStream_t s = (hipStream_t)stream;
+  if (pred_is_mask)
+    launch_clipval_frames<true>(vec, lds, grid, shm, s, pred, (const long long*)labels, count, count_i64, T, C, HW, K, (int)ignore, hist,
+                                conf, (unsigned long long*)state);
+  else
+    launch_clipval_frames<false>(vec, lds, grid, shm, s, pred, (const long long*)labels, count, count_i64, T, C, HW, K, (int)ignore, hist,
+                                 conf, (unsigned long long*)state);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_clipval_combine(uint32_t* hist, uint32_t* conf, uint32_t* flags, const void* count, int32_t count_i64, int32_t B,
+                                    int32_t T, int32_t K, int32_t min_count, int32_t min_values, uint64_t* counts, int64_t* frames,
+                                    int64_t* state, void* stream) {
+  if (!hist || !conf || !flags || !counts || !frames || !state || B <= 0 || T <= 0 || K <= 0 || min_count < 0 || min_values < 0)
+    return CAVP_ERR_BAD_ARG;
+  if ((long long)B * T > 65535 || K > CAVP_METRICS_MAX_CLASSES) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)hist & 3) || ((uintptr_t)conf & 3) || ((uintptr_t)flags & 3) || ((uintptr_t)counts & 7) || ((uintptr_t)frames & 7) ||
+      ((uintptr_t)state & 7) || !clipval_count_ok(count, count_i64))
+    return CAVP_ERR_ALIGN;
+  const int N = B * T, nbins = (K + 1) * K;
+  hipStream_t s = (hipStream_t)stream;
+  clipval_flags_kernel<<<N, kLabelBins, 0, s>>>(hist, flags, count, count_i64, T, (unsigned)min_count, min_values,
+                                               (unsigned long long*)frames, (unsigned long long*)state);
+  const dim3 grid((nbins + kThreads - 1) / kThreads, (N + kCombineFrames - 1) / kCombineFrames);
+  clipval_combine_kernel<<<grid, kThreads, 0, s>>>(conf, flags, N, nbins, (unsigned long long*)counts);
   CHECK_LAUNCH();
 }

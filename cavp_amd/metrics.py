@@ -20,18 +20,22 @@ Differences from the reference, on purpose:
 Additions: `update_lowres(lo, y)` (the same counts from the model's low-resolution logits, CAVP.predict_lowres: the full-resolution
 logits are never written), `update(x, y)` (no host sync; no allocation after the first call, so it can be captured in a hipGraph with the eval
 forward), `reset()`, `counts()` (the device-side (K+1) x K confusion counts) and `fmeasure_curve(...)` (the score curve as a
-device tensor, without `.item()`)."""
+device tensor, without `.item()`), and `ClipValidation`: the validation loop of the AVSS trainers (trainer_cavp_avss_image.py:295-349)
+for whole batches of clips - every frame counted into an ALL matrix and, when its own label histogram says "multi-source", into an
+MS matrix as well, decided on the device."""
 from __future__ import annotations
 
 import numpy
 import torch
 
-from . import ops
+import ctypes as C
+
+from . import _lib, ops
 from ._lib import CavpError
 from .train_ops import zero_ as _zero_
 from .train_ops import zeros as _zeros
 
-__all__ = ["MIoU", "ForegroundDetect", "get_performance", "mask_iou", "Eval_Fmeasure", "fmeasure_curve"]
+__all__ = ["MIoU", "ForegroundDetect", "get_performance", "mask_iou", "Eval_Fmeasure", "fmeasure_curve", "ClipValidation"]
 
 
 def get_performance(miou_measure_in, fg_measure_in, class_list=None):
@@ -48,6 +52,12 @@ def iou_and_accuracy(M: numpy.ndarray):
     union = M.sum(0) + M[:k].sum(1) - hits
     eps = numpy.spacing(1)
     return hits, union, hits.astype(numpy.float64) / (union + eps), float(numpy.trace(M[:k])) / (M.sum() + eps)
+
+
+def pixel_scores(iou: numpy.ndarray, acc, class_list=None):
+    """(mIoU, acc) rounded to 4 decimals from the per-class IoU and the accuracy; mIoU over `class_list` when given."""
+    iou = iou if class_list is None else iou[class_list]
+    return numpy.round(iou.mean().item(), 4), numpy.round(acc, 4)
 
 
 def detection_scores(cm: torch.Tensor, class_list=None):
@@ -118,6 +128,15 @@ class _Confusion:
     def _host_counts(self) -> numpy.ndarray:
         return self.counts().cpu().numpy()
 
+    def _adopt(self, M: torch.Tensor):
+        """Read the (K+1) * K int64 counts `M` that someone else owns and updates (ClipValidation) instead of counts of its own:
+        no copy, every read of this object sees M's current values."""
+        k = self.num_classes
+        if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
+            raise CavpError(f"_adopt: a dense int64 tensor of {(k + 1) * k} counts required")
+        self._M = M.view(-1)
+        return self
+
 
 class MIoU(_Confusion):
     """Mean IoU and pixel accuracy over all batches seen (labels == ignore_index and negative labels are not counted)."""
@@ -142,8 +161,7 @@ class MIoU(_Confusion):
     def get_metric_results(self, class_list=None):
         """(mIoU, acc) rounded to 4 decimals; mIoU over `class_list` when given."""
         self._refresh()
-        iou = self.iou if class_list is None else self.iou[class_list]
-        return numpy.round(iou.mean().item(), 4), numpy.round(self.acc, 4)
+        return pixel_scores(self.iou, self.acc, class_list)
 
     def __call__(self, x, y):
         self.update(x, y)
@@ -260,3 +278,185 @@ def Eval_Fmeasure(pred, gt, measure_path="", pr_num=255, channel=1):
     place) or logits [N, C, H, W] (softmax channel `channel` taken in the kernel); gt: binary mask [N, H, W].  measure_path is
     accepted and unused."""
     return fmeasure_curve(pred, gt, pr_num, channel).max().item()
+
+
+MAX_CLASSES = 4096                 # CAVP_METRICS_MAX_CLASSES
+MAX_CLIP_FRAMES = 65535            # frames of one update(): the launch grid's second dimension
+MAX_CLIP_SCRATCH = 4 << 30         # bytes of per-frame scratch one ClipValidation may ask for
+
+
+class ClipValidation:
+    """The validation loop of the AVSS trainers (trainer_cavp_avss_image.py:295-349) for whole batches of clips, without the host:
+
+        cv = ClipValidation(num_classes=K, ignore_index=255, min_count=100, min_values=2, max_frames=320, device="cuda:0")
+        cv.update(model.predict(image, audio), labels, count)
+        (miou, acc, fdr, f1, f03), (miou_ms, acc_ms, fdr_ms, f1_ms, f03_ms) = cv.results()
+
+    labels: dense int64 [B, T, H, W] (or [N, H, W] with count=None); never written.  pred: the dense uint8 class mask [B*T, H, W]
+    of CAVP.predict, or dense float32 logits [B*T, C, H, W] (argmax: first maximal index, a NaN is the maximum).  count: device
+    int32 / int64 [B], the reference's mask_num per clip: frame t of clip b takes part iff t < count[b] (None: every frame); a
+    frame that takes no part is not read.
+
+    Every participating frame adds its confusion counts (the (K+1) x K bin rule of MIoU / ForegroundDetect) to the ALL matrix.  It
+    is multi-source, and adds them to the MS matrix too, iff more than `min_values` distinct label values have more than
+    `min_count` pixels in it - the reference's `uniq_id[count > 100].shape[0] > 2` on the frame's raw label: the ignore value is a
+    value (negative labels fall into its bin: the reference's MIoU has turned 255 into -1 by then), values >= K are values of their
+    own, the domain is [0, 256).  A pixel whose label is >= 256 or whose mask byte is >= K sets no bin at all, a count[b] outside
+    [0, T] is clamped; each is counted on the device, and check() raises if there were any.
+
+    update() does no host sync and allocates nothing after the first call: it can be captured in a hipGraph with CAVP.predict
+    (run one eager update first).  Three launches (csrc/metrics.hip); integer adds only, so the counts do not depend
+    on arrival order.  all_miou / all_fg / ms_miou / ms_fg are MIoU / ForegroundDetect objects that read the device counts of this
+    object (no copies)."""
+
+    def __init__(self, num_classes: int, ignore_index: int = 255, min_count: int = 100, min_values: int = 2, max_frames: int = 320,
+                 device=None):
+        k = int(num_classes)
+        if not 1 <= k <= MAX_CLASSES:
+            raise CavpError(f"ClipValidation: 1 <= num_classes <= {MAX_CLASSES}, got {num_classes}")
+        if ignore_index is None or not 0 <= int(ignore_index) < 256:
+            raise CavpError(f"ClipValidation: 0 <= ignore_index < 256, got {ignore_index}")
+        if int(min_count) < 0 or int(min_values) < 0 or int(min_count) >= 2 ** 31 or int(min_values) >= 2 ** 31:
+            raise CavpError("ClipValidation: min_count and min_values are non-negative int32 values")
+        if not 1 <= int(max_frames) <= MAX_CLIP_FRAMES:
+            raise CavpError(f"ClipValidation: 1 <= max_frames <= {MAX_CLIP_FRAMES}")
+        self.num_classes, self.ignore_index = k, int(ignore_index)
+        self.min_count, self.min_values, self.max_frames = int(min_count), int(min_values), int(max_frames)
+        self.nbins = (k + 1) * k
+        self.scratch_bytes = self.max_frames * (self.nbins + 256) * 4
+        if self.scratch_bytes > MAX_CLIP_SCRATCH:
+            raise CavpError(f"ClipValidation: {self.scratch_bytes} bytes of per-frame scratch for num_classes={k}, "
+                            f"max_frames={max_frames}; lower max_frames")
+        self._device = device
+        self._counts = None          # device buffers, allocated by the first update (the constructor touches no device)
+        self.all_miou, self.ms_miou = (MIoU(k, self.ignore_index, 0) for _ in range(2))
+        self.all_fg, self.ms_fg = (ForegroundDetect(k, self.ignore_index, 0) for _ in range(2))
+
+    # ---- device state ------------------------------------------------------------------------------------------------------
+    def _bind(self, hist, conf, flags, counts, frames, state):
+        """Take the device buffers: hist u32 [max_frames, 256] and conf u32 [max_frames, (K+1)K] (as int32; zero at rest), flags
+        [max_frames] int32, counts int64 [2, K+1, K], frames int64 [2], state int64 [4]; the four accessors read `counts`."""
+        k, mf = self.num_classes, self.max_frames
+        want = ((hist, torch.int32, mf * 256), (conf, torch.int32, mf * self.nbins), (flags, torch.int32, mf),
+                (counts, torch.int64, 2 * self.nbins), (frames, torch.int64, 2), (state, torch.int64, 4))
+        for t, dt, numel in want:
+            if t.dtype != dt or t.numel() != numel or not t.is_contiguous() or not t.is_cuda or t.device != hist.device:
+                raise CavpError("ClipValidation: device buffers of the wrong dtype, size or device")
+        self.device = hist.device
+        self._hist, self._conf, self._flags, self._frames, self._state = hist, conf, flags, frames, state
+        self._counts = counts.view(2, k + 1, k)
+        self.all_miou._adopt(self._counts[0])
+        self.all_fg._adopt(self._counts[0])
+        self.ms_miou._adopt(self._counts[1])
+        self.ms_fg._adopt(self._counts[1])
+
+    def _ensure(self):
+        if self._counts is None:
+            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            if dev.type != "cuda":
+                raise CavpError("ClipValidation lives on a HIP device (there is no CPU fallback)")
+            if torch.cuda.is_current_stream_capturing():
+                raise CavpError("ClipValidation would allocate during hipGraph capture; run one eager update first")
+            mf = self.max_frames
+            self._bind(_zeros((mf, 256), torch.int32, dev), _zeros((mf, self.nbins), torch.int32, dev),
+                       _zeros((mf,), torch.int32, dev), _zeros((2 * self.nbins,), torch.int64, dev),
+                       _zeros((2,), torch.int64, dev), _zeros((4,), torch.int64, dev))
+
+    # ---- the update --------------------------------------------------------------------------------------------------------
+    def _check_inputs(self, pred, labels, count):
+        E = CavpError
+        if not isinstance(pred, torch.Tensor) or not isinstance(labels, torch.Tensor):
+            raise E("ClipValidation: pred and labels are tensors")
+        if labels.dtype != torch.int64 or labels.dim() not in (3, 4):
+            raise E(f"ClipValidation: labels must be int64 [B, T, H, W] (or [N, H, W] without count), got {labels.dtype} "
+                    f"{tuple(labels.shape)}")
+        if labels.dim() == 3 and count is not None:
+            raise E("ClipValidation: count needs labels [B, T, H, W]")
+        B, T = (labels.shape[0], labels.shape[1]) if labels.dim() == 4 else (1, labels.shape[0])
+        H, W = labels.shape[-2:]
+        N = B * T
+        if N < 1 or H < 1 or W < 1:
+            raise E("ClipValidation: empty labels are not supported")
+        if N > self.max_frames:
+            raise E(f"ClipValidation: {N} frames in one update, max_frames = {self.max_frames}")
+        is_mask = pred.dtype == torch.uint8
+        if is_mask:
+            if tuple(pred.shape) != (N, H, W):
+                raise E(f"ClipValidation: a uint8 class mask of shape {(N, H, W)} required, got {tuple(pred.shape)}")
+            c = 0
+        elif pred.dtype == torch.float32:
+            if pred.dim() != 4 or pred.shape[0] != N or tuple(pred.shape[2:]) != (H, W):
+                raise E(f"ClipValidation: float32 logits [{N}, C, {H}, {W}] required, got {tuple(pred.shape)}")
+            c = pred.shape[1]
+            if not 1 <= c <= self.num_classes:
+                raise E(f"ClipValidation: num_classes {self.num_classes} < logit channels {c}")
+        else:
+            raise E(f"ClipValidation: pred is a uint8 class mask [N, H, W] or float32 logits [N, C, H, W], got {pred.dtype}")
+        if count is not None:
+            if not isinstance(count, torch.Tensor) or count.dtype not in (torch.int32, torch.int64) or tuple(count.shape) != (B,):
+                raise E(f"ClipValidation: count must be an int32 or int64 tensor of shape ({B},)")
+        if not (pred.is_contiguous() and labels.is_contiguous() and (count is None or count.is_contiguous())):
+            raise E("ClipValidation: dense (contiguous) tensors required")
+        ops._need_gpu(pred, labels, count)
+        return B, T, c, H * W, is_mask
+
+    def update(self, pred: torch.Tensor, labels: torch.Tensor, count=None) -> None:
+        """Count one batch of clips (see the class docstring).  No host sync; graph replays of a captured update() accumulate the
+        same way."""
+        B, T, c, HW, is_mask = self._check_inputs(pred, labels, count)
+        self._ensure()
+        for t in (pred, labels, count):
+            if t is not None and t.device != self.device:
+                raise CavpError(f"ClipValidation lives on {self.device}, got a tensor on {t.device}")
+        lib = _lib.load()
+        st = C.c_void_p(ops._stream())
+        i64 = 1 if count is not None and count.dtype == torch.int64 else 0
+        k = self.num_classes
+        _lib.check(lib.cavp_clipval_frame_counts(ops._ptr(pred.detach()), 1 if is_mask else 0, ops._ptr(labels), ops._ptr(count), i64,
+                                                 B, T, c, HW, k, self.ignore_index, ops._ptr(self._hist), ops._ptr(self._conf),
+                                                 ops._ptr(self._state), st), f"cavp_clipval_frame_counts B{B} T{T} C{c} HW{HW} K{k}")
+        _lib.check(lib.cavp_clipval_combine(ops._ptr(self._hist), ops._ptr(self._conf), ops._ptr(self._flags), ops._ptr(count), i64,
+                                            B, T, k, self.min_count, self.min_values, ops._ptr(self._counts), ops._ptr(self._frames),
+                                            ops._ptr(self._state), st), f"cavp_clipval_combine B{B} T{T} K{k}")
+
+    # ---- reading -----------------------------------------------------------------------------------------------------------
+    def counts(self) -> torch.Tensor:
+        """int64 [2, K+1, K] (ALL, MS) on the device; zeros on the CPU before the first update."""
+        if self._counts is None:
+            return torch.zeros((2, self.num_classes + 1, self.num_classes), dtype=torch.int64)
+        return self._counts
+
+    def frames(self):
+        """(frames counted into ALL, frames counted into MS) as Python ints: one host read."""
+        if self._counts is None:
+            return 0, 0
+        a, m = self._frames.cpu().tolist()
+        return a, m
+
+    def results(self, class_list=None):
+        """((mIoU, acc, fdr, f1, f0.3) of ALL, the same of MS): get_performance(all_miou, all_fg, class_list) and
+        get_performance(ms_miou, ms_fg, class_list) from ONE host copy of the counts."""
+        M = self.counts().cpu().numpy()
+        k = self.num_classes
+        out = []
+        for m in M:
+            _, _, iou, acc = iou_and_accuracy(m)
+            out.append((*pixel_scores(iou, acc, class_list), *detection_scores(torch.tensor(m[:k].astype(numpy.float64)), class_list)))
+        return tuple(out)
+
+    def reset(self) -> None:
+        """Zero both matrices and the frame counters (the bad-input counters stay until check())."""
+        if self._counts is not None:
+            _zero_(self._counts)
+            _zero_(self._frames)
+
+    def check(self) -> None:
+        """Synchronises and raises CavpError if, since the last check, a label was >= 256, a mask byte >= num_classes or a count
+        outside [0, T]."""
+        if self._counts is None:
+            raise CavpError("check: no ClipValidation update yet")
+        bad = self._state.cpu().tolist()
+        if any(bad[:3]):
+            _zero_(self._state)
+            raise CavpError(f"ClipValidation: {bad[0]} label(s) >= 256, {bad[1]} mask value(s) >= {self.num_classes}, "
+                            f"{bad[2]} count(s) outside [0, T] since the last check")

@@ -777,6 +777,36 @@ int cavp_labels_scan(const void* label, int32_t label_u8, int32_t B, int64_t HW,
 int cavp_labels_expand(uint32_t* mask, uint32_t* raw_mask, int32_t B, int32_t K, int32_t any_foreground, int64_t* img_label,
                        void* stream);
 
+/* ---- Clip validation (two entry points added to ABI 16; nothing else changed): the validation loop of the AVSS trainers
+ * (trainer_cavp_avss_image.py:295-349) for a batch of B clips of T frames at once, restated in tests/_clipval_ref.py ----
+ * Frame n = b * T + t takes part iff t < clamp(count[b], 0, T) (count: device int32 [B], or int64 with count_i64 != 0; NULL: all
+ * frames).  A frame that does not take part is not read.  Every pixel of a participating frame has a label v (labels: dense int64
+ * [B*T][HW], never written) and a prediction p: pred_is_mask == 0: pred is dense f32 logits [B*T][C][HW] (any 4-byte aligned
+ * base), p = argmax over C (first maximal index, a NaN counts as the maximum); pred_is_mask != 0: pred is a dense u8 class mask
+ * [B*T][HW] (C is ignored).  16-byte loads when HW % 4 == 0 and the bases are aligned (mask: 4 bytes), element loads otherwise.
+ *
+ * cavp_clipval_frame_counts adds, per participating frame, into the per-frame scratch (u32, u32 atomics):
+ *   hist[n][256]      the label histogram: bin v for 0 <= v < 256, bin `ignore` for v < 0;
+ *   conf[n][(K+1)*K]  the confusion counts with the bin rule of the NCHW confusion entry point above (v < 0 or v == ignore: no
+ *                     count; row = v < K ? v : K).
+ *   A pixel with v >= 256 or with a mask byte p >= K is counted in state[0] resp. state[1] and sets no bin in either array: no
+ *   label or mask value indexes memory unguarded.  K >= C, K <= CAVP_METRICS_MAX_CLASSES, 0 <= ignore < 256.
+ * cavp_clipval_combine, per participating frame: the frame is multi-source iff #{v in [0, 256) : hist[n][v] > min_count} >
+ *   min_values (the ignore value counts as a value; values >= K are values of their own).  counts[0] (ALL) += conf[n] for every
+ *   participating frame, counts[1] (MS) += conf[n] for the multi-source ones (counts: u64 [2][(K+1)*K]); frames[0] / frames[1] +=
+ *   the number of frames added to ALL / MS (int64 [2]); state[2] += the count[b] outside [0, T].  flags: u32 [B*T] work array
+ *   (overwritten).  Writes hist and conf of the participating frames back to zero.
+ * hist and conf must hold at least B*T frames and be ZERO before the first call; combine leaves them zero, so nothing is cleared
+ * outside the launches.  state: int64 [4] (device, persistent) {labels >= 256, mask bytes >= K, bad counts, reserved}.  Launch order
+ * on one stream: frame_counts, combine.  Integer adds only: the result is independent of arrival order.  No allocation, no
+ * synchronisation, no host read of a device value: capturable in a hipGraph. */
+int cavp_clipval_frame_counts(const void* pred, int32_t pred_is_mask, const int64_t* labels, const void* count, int32_t count_i64,
+                              int32_t B, int32_t T, int32_t C, int64_t HW, int32_t K, int64_t ignore, uint32_t* hist, uint32_t* conf,
+                              int64_t* state, void* stream);
+int cavp_clipval_combine(uint32_t* hist, uint32_t* conf, uint32_t* flags, const void* count, int32_t count_i64, int32_t B, int32_t T,
+                         int32_t K, int32_t min_count, int32_t min_values, uint64_t* counts, int64_t* frames, int64_t* state,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
