@@ -1,6 +1,8 @@
 // Host-side helpers shared by the extern "C" entry points of every csrc/*.hip: argument checks, the launch status and the
 // run-time dtype -> element type dispatch.  No device code lives here (that is common.h).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 inline bool dt_ok(int dt) { return dt == CAVP_F32 || dt == CAVP_BF16; }
@@ -23,4 +25,14 @@ inline void cavp_dispatch_dtype(int dtype, F&& f) {
     f(float{});
   else
     f(bf16_t{});
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag becomes a template argument, true instantiated first:
+//   cavp_dispatch_bool(vec, [&](auto v) { kernel<decltype(v)::value><<<grid, 256, 0, s>>>(x, n); });
+template <typename F>
+inline void cavp_dispatch_bool(bool flag, F&& f) {
+  if (flag)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
 }

@@ -29,7 +29,11 @@ __device__ __forceinline__ void argmax_step(float v, int c, float& best, int& id
   if (v > best || (v != v && best == best)) { best = v; idx = c; }
 }
 
-// Add the (bin, count) pairs of one thread's 4 pixels (bin < 0: nothing).  Wave-uniform call.
+// Add the (bin, count) pairs of one thread's 4 pixels (bin < 0: nothing).  It ballots and shuffles across the wave, so it is called
+// by all lanes, once per trip, trip count block-uniform: every kernel below walks its quads as
+//   for (base = first quad of the workgroup; base < total; base += quads per grid pass) {
+//     q = base + threadIdx.x;  bins = -1;  if (q < total) { bins of quad q }  add_bins(bins);  }
+// and never calls it under a per-thread condition (a thread without a quad brings bins of -1).
 template <bool kLds, typename G>
 __device__ __forceinline__ void add_bins(int b[4], unsigned* lds, G* gM) {
   int cnt[4];
@@ -80,73 +84,105 @@ __device__ __forceinline__ int conf_bin(LT tv, int p, int K, long long ignore) {
   return row * K + p;
 }
 
-// One thread = 4 consecutive pixels of one image ("quad"); the grid strides over all N * ceil(HW/4) quads with a block-uniform trip
-// count, so every wave reaches the ballots of add_bins with all lanes.
+// ---- one thread's 4 consecutive pixels ("quad") ----------------------------------------------------------------------------------
+// kVec: the quad is whole and every array it touches is aligned for one vector access (the host decides); otherwise only its
+// first np pixels exist and are accessed one by one.
+
+// pixels of a quad that starts `left` pixels before the end of its image
+template <bool kVec>
+__device__ __forceinline__ int quad_pixels(long long left) { return kVec ? 4 : (int)(left < 4 ? left : 4); }
+
+// t[j] = p[j] for j < np (0 beyond): two 16-byte loads for int64, one for float32, one 4-byte load for bytes
+template <typename LT, bool kVec>
+__device__ __forceinline__ void load_quad(const LT* p, int np, LT t[4]) {
+  if constexpr (!kVec) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = j < np ? p[j] : (LT)0;
+  } else if constexpr (sizeof(LT) == 8) {
+    const longlong2 t01 = *(const longlong2*)p, t23 = *(const longlong2*)(p + 2);
+    t[0] = t01.x; t[1] = t01.y; t[2] = t23.x; t[3] = t23.y;
+  } else if constexpr (sizeof(LT) == 4) {
+    const float4 t4 = *(const float4*)p;
+    t[0] = t4.x; t[1] = t4.y; t[2] = t4.z; t[3] = t4.w;
+  } else {
+    const unsigned w = *(const unsigned*)p;
+    t[0] = w & 255u; t[1] = (w >> 8) & 255u; t[2] = (w >> 16) & 255u; t[3] = w >> 24;
+  }
+}
+
+// idx[j] = argmax over the C planes (HW apart) of pixel j of the quad at src: first maximal index, a NaN counts as the maximum
+template <bool kVec>
+__device__ __forceinline__ void quad_argmax_nchw(const float* src, int C, long long HW, int np, int idx[4]) {
+  idx[0] = idx[1] = idx[2] = idx[3] = 0;
+  if constexpr (kVec) {
+    float4 best = *(const float4*)src;
+    for (int c = 1; c < C; ++c) {
+      const float4 v = *(const float4*)(src + c * HW);
+      argmax_step(v.x, c, best.x, idx[0]);
+      argmax_step(v.y, c, best.y, idx[1]);
+      argmax_step(v.z, c, best.z, idx[2]);
+      argmax_step(v.w, c, best.w, idx[3]);
+    }
+  } else {
+    float best[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) best[j] = j < np ? src[j] : 0.f;
+    for (int c = 1; c < C; ++c) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < np) argmax_step(src[c * HW + j], c, best[j], idx[j]);
+      }
+    }
+  }
+}
+
+// b[j] = the confusion bin of pixel j (label lab[j], prediction idx[j]), -1 beyond np; vec: one vector access for the labels
+template <typename LT>
+__device__ __forceinline__ void quad_conf_bins(const LT* lab, bool vec, int np, const int idx[4], int K, long long ignore, int b[4]) {
+  LT t[4];
+  if (vec) load_quad<LT, true>(lab, 4, t);
+  else load_quad<LT, false>(lab, np, t);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(t[j], idx[j], K, ignore) : -1;
+}
+
+// ---- a workgroup's u32 counts in LDS: clear, count with add_bins<true>, flush the non-zero ones into global memory ----------------
+__device__ __forceinline__ void lds_counts_clear(unsigned* lds, int n) {
+  for (int i = threadIdx.x; i < n; i += kThreads) lds[i] = 0u;
+  __syncthreads();
+}
+
+template <typename G>
+__device__ __forceinline__ void lds_counts_flush(const unsigned* lds, int n, G* g) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    const unsigned v = lds[i];
+    if (v) atomicAdd(g + i, (G)v);
+  }
+}
+
+// The grid strides over all N * ceil(HW/4) quads, one per thread.
 template <bool kVec, bool kLds, typename LT>
 __global__ __launch_bounds__(kThreads) void seg_confusion_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
                                                                 int N, int C, long long HW, int K, long long ignore,
                                                                 unsigned long long* __restrict__ M) {
   extern __shared__ unsigned hist[];
   const int nbins = (K + 1) * K;
-  if (kLds) {
-    for (int i = threadIdx.x; i < nbins; i += kThreads) hist[i] = 0u;
-    __syncthreads();
-  }
+  if (kLds) lds_counts_clear(hist, nbins);
   const long long nq = (HW + 3) >> 2, total = (long long)N * nq;
   for (long long base = (long long)blockIdx.x * kThreads; base < total; base += (long long)gridDim.x * kThreads) {
     const long long q = base + threadIdx.x;
     int b[4] = {-1, -1, -1, -1};
     if (q < total) {
       const long long n = q / nq, p0 = (q - n * nq) * 4;
-      const float* src = logits + n * C * HW + p0;
-      const LT* lab = labels + n * HW + p0;
-      if (kVec) {
-        float4 best = *(const float4*)src;
-        int i0 = 0, i1 = 0, i2 = 0, i3 = 0;
-        for (int c = 1; c < C; ++c) {
-          const float4 v = *(const float4*)(src + c * HW);
-          argmax_step(v.x, c, best.x, i0);
-          argmax_step(v.y, c, best.y, i1);
-          argmax_step(v.z, c, best.z, i2);
-          argmax_step(v.w, c, best.w, i3);
-        }
-        LT t[4];
-        if constexpr (sizeof(LT) == 8) {
-          const longlong2 t01 = *(const longlong2*)lab, t23 = *(const longlong2*)(lab + 2);
-          t[0] = t01.x; t[1] = t01.y; t[2] = t23.x; t[3] = t23.y;
-        } else {
-          const float4 t4 = *(const float4*)lab;
-          t[0] = t4.x; t[1] = t4.y; t[2] = t4.z; t[3] = t4.w;
-        }
-        b[0] = conf_bin(t[0], i0, K, ignore);
-        b[1] = conf_bin(t[1], i1, K, ignore);
-        b[2] = conf_bin(t[2], i2, K, ignore);
-        b[3] = conf_bin(t[3], i3, K, ignore);
-      } else {
-        const int np = (int)(HW - p0 < 4 ? HW - p0 : 4);
-        float best[4];
-        int idx[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) best[j] = j < np ? src[j] : 0.f;
-        for (int c = 1; c < C; ++c) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (j < np) argmax_step(src[c * HW + j], c, best[j], idx[j]);
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(lab[j], idx[j], K, ignore) : -1;
-      }
+      const int np = quad_pixels<kVec>(HW - p0);
+      int idx[4];
+      quad_argmax_nchw<kVec>(logits + n * C * HW + p0, C, HW, np, idx);
+      quad_conf_bins(labels + n * HW + p0, kVec, np, idx, K, ignore, b);
     }
     add_bins<kLds>(b, hist, M);
   }
-  if (kLds) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < nbins; i += kThreads) {
-      const unsigned v = hist[i];
-      if (v) atomicAdd(M + i, (unsigned long long)v);
-    }
-  }
+  if (kLds) lds_counts_flush(hist, nbins, M);
 }
 
 template <typename T>
@@ -190,8 +226,7 @@ __global__ __launch_bounds__(kThreads) void fmeasure_hist_kernel(const float* __
   unsigned* h0 = smem + pr_num;
   unsigned* h1 = h0 + pr_num + 1;
   for (int i = threadIdx.x; i < pr_num; i += kThreads) s_th[i] = th[i];
-  for (int i = threadIdx.x; i < 2 * (pr_num + 1); i += kThreads) h0[i] = 0u;
-  __syncthreads();
+  lds_counts_clear(h0, 2 * (pr_num + 1));   // h0 and h1; its barrier covers s_th too
   const long long n = blockIdx.y;
   const TG* G = gt + n * HW;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < HW; i += (long long)gridDim.x * kThreads) {
@@ -214,12 +249,7 @@ __global__ __launch_bounds__(kThreads) void fmeasure_hist_kernel(const float* __
     atomicAdd(h0 + lo, 1u);
     if (G[i] != (TG)0) atomicAdd(h1 + lo, 1u);
   }
-  __syncthreads();
-  unsigned* out = hist + n * 2 * (pr_num + 1);
-  for (int i = threadIdx.x; i < 2 * (pr_num + 1); i += kThreads) {
-    const unsigned v = h0[i];
-    if (v) atomicAdd(out + i, v);
-  }
+  lds_counts_flush(h0, 2 * (pr_num + 1), hist + n * 2 * (pr_num + 1));
 }
 
 int chunks_for(long long work, long long per_block, int cap) {
@@ -308,10 +338,7 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(const T* __restri
                                                               unsigned long long* __restrict__ M, int out_vec) {
   extern __shared__ unsigned hist[];
   const int nbins = (K + 1) * K;
-  if (kConf == 1) {
-    for (int i = threadIdx.x; i < nbins; i += kThreads) hist[i] = 0u;
-    __syncthreads();
-  }
+  if (kConf == 1) lds_counts_clear(hist, nbins);
   const int qpr = (Wo + 3) >> 2;
   const long long total = (long long)N * Ho * qpr;
   for (long long base = (long long)blockIdx.x * kThreads; base < total; base += (long long)gridDim.x * kThreads) {
@@ -377,46 +404,14 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(const T* __restri
         }
       }
       if (kConf) {
-        if (label_f32) {
-          const float* lab = (const float*)labels + p0;
-          float t[4] = {0.f, 0.f, 0.f, 0.f};
-          if (out_vec & kOutVecLabels) {
-            const float4 t4 = *(const float4*)lab;
-            t[0] = t4.x; t[1] = t4.y; t[2] = t4.z; t[3] = t4.w;
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (j < np) t[j] = lab[j];
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(t[j], idx[j], K, ignore) : -1;
-        } else {
-          const long long* lab = (const long long*)labels + p0;
-          long long t[4] = {0, 0, 0, 0};
-          if (out_vec & kOutVecLabels) {
-            const longlong2 t01 = *(const longlong2*)lab, t23 = *(const longlong2*)(lab + 2);
-            t[0] = t01.x; t[1] = t01.y; t[2] = t23.x; t[3] = t23.y;
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (j < np) t[j] = lab[j];
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) b[j] = j < np ? conf_bin(t[j], idx[j], K, ignore) : -1;
-        }
+        const bool vec = (out_vec & kOutVecLabels) != 0;
+        if (label_f32) quad_conf_bins((const float*)labels + p0, vec, np, idx, K, ignore, b);
+        else quad_conf_bins((const long long*)labels + p0, vec, np, idx, K, ignore, b);
       }
     }
-    if (kConf) add_bins<kConf == 1>(b, hist, M);
+    if constexpr (kConf != 0) add_bins<kConf == 1>(b, hist, M);   // kConf is a template argument: not a per-thread condition
   }
-  if (kConf == 1) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < nbins; i += kThreads) {
-      const unsigned v = hist[i];
-      if (v) atomicAdd(M + i, (unsigned long long)v);
-    }
-  }
+  if (kConf == 1) lds_counts_flush(hist, nbins, M);
 }
 
 // ---- clip validation: the frames of a batch of clips routed into the ALL and the multi-source (MS) matrix ------------------------
@@ -449,8 +444,7 @@ __global__ __launch_bounds__(kThreads) void clipval_frame_kernel(const void* __r
   if (t >= clip_count(count, count_i64, b, T)) return;   // workgroup-uniform: the frame is not read
   const int nbins = (K + 1) * K;
   unsigned* lconf = lds + kLabelBins;
-  for (int i = threadIdx.x; i < kLabelBins + (kLds ? nbins : 0); i += kThreads) lds[i] = 0u;
-  __syncthreads();
+  lds_counts_clear(lds, kLabelBins + (kLds ? nbins : 0));
   unsigned* gconf = conf + (size_t)n * nbins;
   const long long* lab_n = labels + (long long)n * HW;
   const long long nq = (HW + 3) >> 2;
@@ -460,52 +454,17 @@ __global__ __launch_bounds__(kThreads) void clipval_frame_kernel(const void* __r
     int hb[4] = {-1, -1, -1, -1}, cb[4] = {-1, -1, -1, -1};
     if (q < nq) {
       const long long p0 = q * 4;
-      const int np = kVec ? 4 : (int)(HW - p0 < 4 ? HW - p0 : 4);
-      const long long* lab = lab_n + p0;
-      long long tv[4] = {0, 0, 0, 0};
-      int p[4] = {0, 0, 0, 0};
-      if (kVec) {
-        const longlong2 t01 = *(const longlong2*)lab, t23 = *(const longlong2*)(lab + 2);
-        tv[0] = t01.x; tv[1] = t01.y; tv[2] = t23.x; tv[3] = t23.y;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (j < np) tv[j] = lab[j];
-        }
-      }
+      const int np = quad_pixels<kVec>(HW - p0);
+      long long tv[4];
+      load_quad<long long, kVec>(lab_n + p0, np, tv);
+      int p[4];
       if (kMask) {
-        const unsigned char* src = (const unsigned char*)pred + (long long)n * HW + p0;
-        if (kVec) {
-          const unsigned w = *(const unsigned*)src;
-          p[0] = w & 255u; p[1] = (w >> 8) & 255u; p[2] = (w >> 16) & 255u; p[3] = w >> 24;
-        } else {
+        unsigned char m[4];
+        load_quad<unsigned char, kVec>((const unsigned char*)pred + (long long)n * HW + p0, np, m);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (j < np) p[j] = src[j];
-          }
-        }
+        for (int j = 0; j < 4; ++j) p[j] = m[j];
       } else {
-        const float* src = (const float*)pred + (long long)n * C * HW + p0;
-        if (kVec) {
-          float4 best = *(const float4*)src;
-          for (int c = 1; c < C; ++c) {
-            const float4 v = *(const float4*)(src + c * HW);
-            argmax_step(v.x, c, best.x, p[0]);
-            argmax_step(v.y, c, best.y, p[1]);
-            argmax_step(v.z, c, best.z, p[2]);
-            argmax_step(v.w, c, best.w, p[3]);
-          }
-        } else {
-          float best[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) best[j] = j < np ? src[j] : 0.f;
-          for (int c = 1; c < C; ++c) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (j < np) argmax_step(src[c * HW + j], c, best[j], p[j]);
-            }
-          }
-        }
+        quad_argmax_nchw<kVec>((const float*)pred + (long long)n * C * HW + p0, C, HW, np, p);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -522,12 +481,8 @@ __global__ __launch_bounds__(kThreads) void clipval_frame_kernel(const void* __r
   }
   if (bad_label) atomicAdd(state, (unsigned long long)bad_label);
   if (bad_mask) atomicAdd(state + 1, (unsigned long long)bad_mask);
-  __syncthreads();
-  unsigned* ghist = hist + (size_t)n * kLabelBins;
-  for (int i = threadIdx.x; i < kLabelBins + (kLds ? nbins : 0); i += kThreads) {
-    const unsigned v = lds[i];
-    if (v) atomicAdd(i < kLabelBins ? ghist + i : gconf + (i - kLabelBins), v);
-  }
+  lds_counts_flush(lds, kLabelBins, hist + (size_t)n * kLabelBins);
+  if (kLds) lds_counts_flush(lconf, nbins, gconf);
 }
 
 // grid B*T, 256 threads = the 256 histogram bins of one frame.  flags[n]: 0 = takes no part, 1 = ALL, 3 = ALL and MS.
@@ -588,54 +543,64 @@ __global__ __launch_bounds__(kThreads) void clipval_combine_kernel(unsigned* __r
   if (ms) atomicAdd(counts + nbins + i, ms);
 }
 
-}  // namespace
+// ---- host side: the checks the entry points share, run-time arguments -> template arguments -------------------------------------
+bool label_ok(int code) { return code == CAVP_I64 || code == CAVP_F32; }
+bool classes_ok(int K, int C) { return K >= C && K <= CAVP_METRICS_MAX_CLASSES; }
+// p (may be null) is aligned for int64 elements (wide) or for 4-byte ones
+bool aligned_for(const void* p, bool wide) { return ((uintptr_t)p & (wide ? 7 : 3)) == 0; }
+bool label_aligned(const void* p, int code) { return aligned_for(p, code == CAVP_I64); }
+// the (K+1) x K counts of one workgroup fit the u32 LDS histogram; otherwise the kernels add straight into global memory
+bool counts_fit_lds(int K) { return (K + 1) * K <= kLdsBins; }
 
-template <typename LT>
-void launch_confusion(bool vec, bool lds, int grid, size_t shm, hipStream_t s, const float* logits, const LT* lab, int N, int C,
-                      long long HW, int K, long long ignore, unsigned long long* m) {
-  if (vec && lds) seg_confusion_kernel<true, true, LT><<<grid, kThreads, shm, s>>>(logits, lab, N, C, HW, K, ignore, m);
-  else if (vec) seg_confusion_kernel<true, false, LT><<<grid, kThreads, 0, s>>>(logits, lab, N, C, HW, K, ignore, m);
-  else if (lds) seg_confusion_kernel<false, true, LT><<<grid, kThreads, shm, s>>>(logits, lab, N, C, HW, K, ignore, m);
-  else seg_confusion_kernel<false, false, LT><<<grid, kThreads, 0, s>>>(logits, lab, N, C, HW, K, ignore, m);
+// f(LT{}) with LT = long long / float for a label dtype code the caller has validated (label_ok)
+template <typename F>
+void dispatch_label(int code, F&& f) {
+  if (code == CAVP_I64)
+    f((long long)0);
+  else
+    f(0.f);
 }
+
+// seg_predict_kernel's kConf: 0 no counts, 1 counts in LDS, 2 counts straight into M
+template <typename F>
+void dispatch_conf(int conf, F&& f) {
+  if (conf == 0)
+    f(std::integral_constant<int, 0>{});
+  else if (conf == 1)
+    f(std::integral_constant<int, 1>{});
+  else
+    f(std::integral_constant<int, 2>{});
+}
+
+// K = 127: 64 KiB of counts + the 1 KiB label histogram, past the 64 KiB default; once per instantiation
+template <bool kMask, bool kVec, bool kLds>
+void clipval_frame_allow_lds() {
+  static const hipError_t once = hipFuncSetAttribute((const void*)clipval_frame_kernel<kMask, kVec, kLds>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (kLdsBins + kLabelBins) * (int)sizeof(unsigned));
+  (void)once;
+}
+
+}  // namespace
 
 extern "C" int cavp_seg_confusion_nchw(const float* logits, const void* labels, int32_t label_dtype, int32_t N, int32_t C, int64_t HW,
                                        int32_t K, int64_t ignore, uint64_t* M, void* stream) {
   if (!logits || !labels || !M || N <= 0 || C <= 0 || HW <= 0 || K <= 0) return CAVP_ERR_BAD_ARG;
-  if (K < C || K > CAVP_METRICS_MAX_CLASSES) return CAVP_ERR_UNSUPPORTED;
-  const bool li = label_dtype == CAVP_I64;
-  if (!li && label_dtype != CAVP_F32) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)labels & (li ? 7 : 3)) || ((uintptr_t)M & 7) || ((uintptr_t)logits & 3)) return CAVP_ERR_ALIGN;
+  if (!classes_ok(K, C)) return CAVP_ERR_UNSUPPORTED;
+  if (!label_ok(label_dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (!label_aligned(labels, label_dtype) || ((uintptr_t)M & 7) || ((uintptr_t)logits & 3)) return CAVP_ERR_ALIGN;
   const bool vec = (HW & 3) == 0 && al16(logits) && al16(labels);
-  const bool lds = (K + 1) * K <= kLdsBins;
+  const bool lds = counts_fit_lds(K);
   const long long quads = (long long)N * ((HW + 3) >> 2);
   // one quad per thread for B=32 at 224^2 (1568 workgroups, all resident); each workgroup flushes its non-zero LDS bins once
   const int grid = chunks_for(quads, kThreads, lds ? 2048 : 4096);
   const size_t shm = lds ? (size_t)(K + 1) * K * sizeof(unsigned) : 0;
   hipStream_t s = (hipStream_t)stream;
-  unsigned long long* m = (unsigned long long*)M;
-  if (li) launch_confusion(vec, lds, grid, shm, s, logits, (const long long*)labels, N, C, HW, K, ignore, m);
-  else launch_confusion(vec, lds, grid, shm, s, logits, (const float*)labels, N, C, HW, K, ignore, m);
+  dispatch_label(label_dtype, [&](auto t) { using LT = decltype(t);
+    cavp_dispatch_bool(vec, [&](auto v) { cavp_dispatch_bool(lds, [&](auto l) {
+      seg_confusion_kernel<decltype(v)::value, decltype(l)::value, LT><<<grid, kThreads, shm, s>>>(
+          logits, (const LT*)labels, N, C, HW, K, ignore, (unsigned long long*)M); }); }); });
   CHECK_LAUNCH();
-}
-
-template <typename T>
-void launch_seg_predict(bool vec, int conf, int grid, size_t shm, hipStream_t s, const T* x, int N, int Hi, int Wi, int C, int ldx, int Ho,
-                        int Wo, int align, unsigned char* mask, float* prob, int channel, const void* labels, int label_f32, int K,
-                        long long ignore, unsigned long long* M, int out_vec) {
-#define CAVP_SEG_PREDICT(V, CF) \
-  seg_predict_kernel<T, V, CF><<<grid, kThreads, shm, s>>>(x, N, Hi, Wi, C, ldx, Ho, Wo, align, mask, prob, channel, labels, label_f32, K, \
-                                                         ignore, M, out_vec)
-  if (vec) {
-    if (conf == 0) CAVP_SEG_PREDICT(true, 0);
-    else if (conf == 1) CAVP_SEG_PREDICT(true, 1);
-    else CAVP_SEG_PREDICT(true, 2);
-  } else {
-    if (conf == 0) CAVP_SEG_PREDICT(false, 0);
-    else if (conf == 1) CAVP_SEG_PREDICT(false, 1);
-    else CAVP_SEG_PREDICT(false, 2);
-  }
-#undef CAVP_SEG_PREDICT
 }
 
 extern "C" int cavp_seg_predict_nhwc(int32_t dtype, const void* x, int32_t N, int32_t Hi, int32_t Wi, int32_t C, int32_t ldx, int32_t Ho,
@@ -647,12 +612,12 @@ extern "C" int cavp_seg_predict_nhwc(int32_t dtype, const void* x, int32_t N, in
   if (M && K <= 0) return CAVP_ERR_BAD_ARG;
   if (!dt_ok(dtype)) return CAVP_ERR_UNSUPPORTED;
   if (mask && C > 256) return CAVP_ERR_UNSUPPORTED;
-  const bool lf = label_dtype == CAVP_F32;
-  if (M && (K < C || K > CAVP_METRICS_MAX_CLASSES || (!lf && label_dtype != CAVP_I64))) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)x & (dtype == CAVP_F32 ? 3 : 1)) || ((uintptr_t)prob & 3) || ((uintptr_t)labels & (lf ? 3 : 7)) || ((uintptr_t)M & 7))
+  if (M && (!classes_ok(K, C) || !label_ok(label_dtype))) return CAVP_ERR_UNSUPPORTED;
+  // without M there are no labels (null: aligned for any dtype code)
+  if (((uintptr_t)x & (dtype == CAVP_F32 ? 3 : 1)) || ((uintptr_t)prob & 3) || !label_aligned(labels, label_dtype) || ((uintptr_t)M & 7))
     return CAVP_ERR_ALIGN;
   const bool vec = ldx % dt_ve(dtype) == 0 && al16(x);
-  const int conf = !M ? 0 : ((K + 1) * K <= kLdsBins ? 1 : 2);
+  const int conf = !M ? 0 : (counts_fit_lds(K) ? 1 : 2);
   int out_vec = 0;
   if ((Wo & 3) == 0) out_vec = (((uintptr_t)mask & 3) ? 0 : kOutVecMask) | (al16(prob) ? kOutVecProb : 0) | (al16(labels) ? kOutVecLabels : 0);
   const long long quads = (long long)N * Ho * ((Wo + 3) >> 2);
@@ -660,24 +625,23 @@ extern "C" int cavp_seg_predict_nhwc(int32_t dtype, const void* x, int32_t N, in
   const size_t shm = conf == 1 ? (size_t)(K + 1) * K * sizeof(unsigned) : 0;
   hipStream_t s = (hipStream_t)stream;
   cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
-    launch_seg_predict<T>(vec, conf, grid, shm, s, (const T*)x, N, Hi, Wi, C, ldx, Ho, Wo, align_corners, mask, prob, channel, labels, lf, K,
-                          ignore, (unsigned long long*)M, out_vec); });
+    cavp_dispatch_bool(vec, [&](auto v) { dispatch_conf(conf, [&](auto cf) {
+      seg_predict_kernel<T, decltype(v)::value, decltype(cf)::value><<<grid, kThreads, shm, s>>>(
+          (const T*)x, N, Hi, Wi, C, ldx, Ho, Wo, align_corners, mask, prob, channel, labels, label_dtype == CAVP_F32, K, ignore,
+          (unsigned long long*)M, out_vec); }); }); });
   CHECK_LAUNCH();
 }
 
 extern "C" int cavp_mask_iou_stats(const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype, int32_t N,
                                    int64_t HW, int64_t* out, void* stream) {
   if (!pred || !target || !out || N <= 0 || HW <= 0) return CAVP_ERR_BAD_ARG;
-  const bool pi = pred_dtype == CAVP_I64, ti = target_dtype == CAVP_I64;
-  if ((!pi && pred_dtype != CAVP_F32) || (!ti && target_dtype != CAVP_F32)) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)pred & (pi ? 7 : 3)) || ((uintptr_t)target & (ti ? 7 : 3)) || ((uintptr_t)out & 7)) return CAVP_ERR_ALIGN;
+  if (!label_ok(pred_dtype) || !label_ok(target_dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (!label_aligned(pred, pred_dtype) || !label_aligned(target, target_dtype) || ((uintptr_t)out & 7)) return CAVP_ERR_ALIGN;
   const dim3 grid(chunks_for(HW, 4 * kThreads, 256), N);
   hipStream_t s = (hipStream_t)stream;
-  unsigned long long* o = (unsigned long long*)out;
-  if (pi && ti) mask_iou_stats_kernel<long long, long long><<<grid, kThreads, 0, s>>>((const long long*)pred, (const long long*)target, HW, o);
-  else if (pi) mask_iou_stats_kernel<long long, float><<<grid, kThreads, 0, s>>>((const long long*)pred, (const float*)target, HW, o);
-  else if (ti) mask_iou_stats_kernel<float, long long><<<grid, kThreads, 0, s>>>((const float*)pred, (const long long*)target, HW, o);
-  else mask_iou_stats_kernel<float, float><<<grid, kThreads, 0, s>>>((const float*)pred, (const float*)target, HW, o);
+  dispatch_label(pred_dtype, [&](auto p) { using TP = decltype(p);
+    dispatch_label(target_dtype, [&](auto t) { using TT = decltype(t);
+      mask_iou_stats_kernel<TP, TT><<<grid, kThreads, 0, s>>>((const TP*)pred, (const TT*)target, HW, (unsigned long long*)out); }); });
   CHECK_LAUNCH();
 }
 
@@ -687,40 +651,15 @@ extern "C" int cavp_fmeasure_hist(const float* src, int64_t src_image_stride, co
   if (C >= 2 && (channel < 0 || channel >= C)) return CAVP_ERR_BAD_ARG;
   if (src_image_stride < (C >= 2 ? (int64_t)C * HW : HW) && N > 1) return CAVP_ERR_BAD_ARG;
   if (pr_num > CAVP_FMEASURE_MAX_THRESHOLDS) return CAVP_ERR_UNSUPPORTED;
-  const bool gi = gt_dtype == CAVP_I64;
-  if (!gi && gt_dtype != CAVP_F32) return CAVP_ERR_UNSUPPORTED;
-  if (((uintptr_t)src & 3) || ((uintptr_t)gt & (gi ? 7 : 3)) || ((uintptr_t)thresholds & 3) || ((uintptr_t)hist & 3)) return CAVP_ERR_ALIGN;
+  if (!label_ok(gt_dtype)) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)src & 3) || !label_aligned(gt, gt_dtype) || ((uintptr_t)thresholds & 3) || ((uintptr_t)hist & 3)) return CAVP_ERR_ALIGN;
   const dim3 grid(chunks_for(HW, 4 * kThreads, 256), N);
   const size_t shm = (size_t)(pr_num + 2 * (pr_num + 1)) * sizeof(unsigned);
   hipStream_t s = (hipStream_t)stream;
-  if (gi) fmeasure_hist_kernel<long long><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const long long*)gt, thresholds, C, channel, HW, pr_num, hist);
-  else fmeasure_hist_kernel<float><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const float*)gt, thresholds, C, channel, HW, pr_num, hist);
+  dispatch_label(gt_dtype, [&](auto g) { using TG = decltype(g);
+    fmeasure_hist_kernel<TG><<<grid, kThreads, shm, s>>>(src, src_image_stride, (const TG*)gt, thresholds, C, channel, HW, pr_num, hist); });
   CHECK_LAUNCH();
 }
-
-template <bool kMask>
-void launch_clipval_frames(bool vec, bool lds, dim3 grid, size_t shm, hipStream_t s, const void* pred, const long long* labels,
-                           const void* count, int count_i64, int T, int C, long long HW, int K, int ignore, unsigned* hist, unsigned* conf,
-                           unsigned long long* state) {
-#define CAVP_CLIPVAL(V, L)                                                                                                         \
-  do {                                                                                                                             \
-    static bool attr_set = false; /* K = 127: 64 KiB of counts + the 1 KiB histogram, past the 64 KiB default */                    \
-    if (!attr_set) {                                                                                                               \
-      (void)hipFuncSetAttribute((const void*)clipval_frame_kernel<kMask, V, L>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                (kLdsBins + kLabelBins) * (int)sizeof(unsigned));                                                   \
-      attr_set = true;                                                                                                             \
-    }                                                                                                                              \
-    clipval_frame_kernel<kMask, V, L><<<grid, kThreads, shm, s>>>(pred, labels, count, count_i64, T, C, HW, K, ignore, hist, conf, \
-                                                                   state);                                                         \
-  } while (0)
-  if (vec && lds) CAVP_CLIPVAL(true, true);
-  else if (vec) CAVP_CLIPVAL(true, false);
-  else if (lds) CAVP_CLIPVAL(false, true);
-  else CAVP_CLIPVAL(false, false);
-#undef CAVP_CLIPVAL
-}
-
-static bool clipval_count_ok(const void* count, int32_t count_i64) { return !count || !((uintptr_t)count & (count_i64 ? 7 : 3)); }
 
 extern "C" int cavp_clipval_frame_counts(const void* pred, int32_t pred_is_mask, const int64_t* labels, const void* count,
                                          int32_t count_i64, int32_t B, int32_t T, int32_t C, int64_t HW, int32_t K, int64_t ignore,
@@ -729,22 +668,21 @@ extern "C" int cavp_clipval_frame_counts(const void* pred, int32_t pred_is_mask,
     return CAVP_ERR_BAD_ARG;
   if (ignore < 0 || ignore >= kLabelBins) return CAVP_ERR_BAD_ARG;
   if ((long long)B * T > 65535 || HW > 0x7fffffffLL) return CAVP_ERR_UNSUPPORTED;   // grid.y; u32 counts per frame
-  if (K > CAVP_METRICS_MAX_CLASSES || (!pred_is_mask && K < C)) return CAVP_ERR_UNSUPPORTED;
+  if (!classes_ok(K, pred_is_mask ? 0 : C)) return CAVP_ERR_UNSUPPORTED;            // a mask has no channels
   if (((uintptr_t)labels & 7) || ((uintptr_t)hist & 3) || ((uintptr_t)conf & 3) || ((uintptr_t)state & 7) ||
-      (!pred_is_mask && ((uintptr_t)pred & 3)) || !clipval_count_ok(count, count_i64))
+      (!pred_is_mask && ((uintptr_t)pred & 3)) || !aligned_for(count, count_i64 != 0))
     return CAVP_ERR_ALIGN;
   const bool vec = (HW & 3) == 0 && al16(labels) && (pred_is_mask ? ((uintptr_t)pred & 3) == 0 : al16(pred));
-  const bool lds = (K + 1) * K <= kLdsBins;
+  const bool lds = counts_fit_lds(K);
   // 2 quads per thread (25 workgroups per frame at 224^2): enough workgroups for a single clip, few enough LDS clears and flushes
   const dim3 grid(chunks_for((HW + 3) >> 2, 2 * kThreads, 64), B * T);
   const size_t shm = (size_t)(kLabelBins + (lds ? (K + 1) * K : 0)) * sizeof(unsigned);
   hipStream_t s = (hipStream_t)stream;
-  if (pred_is_mask)
-    launch_clipval_frames<true>(vec, lds, grid, shm, s, pred, (const long long*)labels, count, count_i64, T, C, HW, K, (int)ignore, hist,
-                                conf, (unsigned long long*)state);
-  else
-    launch_clipval_frames<false>(vec, lds, grid, shm, s, pred, (const long long*)labels, count, count_i64, T, C, HW, K, (int)ignore, hist,
-                                 conf, (unsigned long long*)state);
+  cavp_dispatch_bool(pred_is_mask != 0, [&](auto m) { cavp_dispatch_bool(vec, [&](auto v) { cavp_dispatch_bool(lds, [&](auto l) {
+    constexpr bool kMask = decltype(m)::value, kVec = decltype(v)::value, kLds = decltype(l)::value;
+    clipval_frame_allow_lds<kMask, kVec, kLds>();
+    clipval_frame_kernel<kMask, kVec, kLds><<<grid, kThreads, shm, s>>>(pred, (const long long*)labels, count, count_i64, T, C, HW, K,
+                                                                        (int)ignore, hist, conf, (unsigned long long*)state); }); }); });
   CHECK_LAUNCH();
 }
 
@@ -753,9 +691,9 @@ extern "C" int cavp_clipval_combine(uint32_t* hist, uint32_t* conf, uint32_t* fl
                                     int64_t* state, void* stream) {
   if (!hist || !conf || !flags || !counts || !frames || !state || B <= 0 || T <= 0 || K <= 0 || min_count < 0 || min_values < 0)
     return CAVP_ERR_BAD_ARG;
-  if ((long long)B * T > 65535 || K > CAVP_METRICS_MAX_CLASSES) return CAVP_ERR_UNSUPPORTED;
+  if ((long long)B * T > 65535 || !classes_ok(K, 0)) return CAVP_ERR_UNSUPPORTED;
   if (((uintptr_t)hist & 3) || ((uintptr_t)conf & 3) || ((uintptr_t)flags & 3) || ((uintptr_t)counts & 7) || ((uintptr_t)frames & 7) ||
-      ((uintptr_t)state & 7) || !clipval_count_ok(count, count_i64))
+      ((uintptr_t)state & 7) || !aligned_for(count, count_i64 != 0))
     return CAVP_ERR_ALIGN;
   const int N = B * T, nbins = (K + 1) * K;
   hipStream_t s = (hipStream_t)stream;

@@ -28,9 +28,7 @@ from __future__ import annotations
 import numpy
 import torch
 
-import ctypes as C
-
-from . import _lib, ops
+from . import ops
 from ._lib import CavpError
 from .train_ops import zero_ as _zero_
 from .train_ops import zeros as _zeros
@@ -85,6 +83,13 @@ class _Confusion:
         self._kernel_ignore = -1 if ignore is None else int(ignore)   # -1 is never a valid label (t >= 0)
         self._M = None
 
+    def _counts_on(self, device) -> torch.Tensor:
+        """The counts the kernels add into: zeros on `device` at the first update (and after a change of device)."""
+        if self._M is None or self._M.device != device:
+            k = self.num_classes
+            self._M = _zeros(((k + 1) * k,), torch.int64, device)
+        return self._M
+
     def update(self, x: torch.Tensor, y: torch.Tensor) -> None:
         """Accumulate one batch: x logits [B, C, H, W] (float32), y labels [B, H, W] (int64, or float32 holding integers).
         No host sync; graph replays of a captured update() accumulate the same way."""
@@ -92,10 +97,7 @@ class _Confusion:
             raise CavpError(f"{type(self).__name__}: logits [B, C, H, W] and target [B, H, W] required, got "
                             f"{tuple(x.shape)} / {tuple(y.shape)}")
         ops._need_gpu(x, y)
-        k = self.num_classes
-        if self._M is None or self._M.device != x.device:
-            self._M = _zeros(((k + 1) * k,), torch.int64, x.device)
-        ops.seg_confusion(x.detach(), y, k, self._kernel_ignore, self._M)
+        ops.seg_confusion(x.detach(), y, self.num_classes, self._kernel_ignore, self._counts_on(x.device))
 
     def update_lowres(self, lo: torch.Tensor, y: torch.Tensor, input_shape=None, align_corners: bool = False) -> None:
         """update() from the low-resolution logits `lo` (NHWC view [B, h, w, C], f32 or bf16: CAVP.predict_lowres): the counts of
@@ -108,11 +110,8 @@ class _Confusion:
         if shape != tuple(y.shape[1:]):
             raise CavpError(f"{type(self).__name__}: input_shape {shape} differs from the target's {tuple(y.shape[1:])}")
         ops._need_gpu(lo, y)
-        k = self.num_classes
-        if self._M is None or self._M.device != lo.device:
-            self._M = _zeros(((k + 1) * k,), torch.int64, lo.device)
-        ops.seg_predict(lo.detach(), shape, labels=y, num_classes=k, ignore=self._kernel_ignore, M=self._M,
-                        align_corners=align_corners)
+        ops.seg_predict(lo.detach(), shape, labels=y, num_classes=self.num_classes, ignore=self._kernel_ignore,
+                        M=self._counts_on(lo.device), align_corners=align_corners)
 
     def counts(self) -> torch.Tensor:
         """The (K+1) x K confusion counts (int64, on the device; zeros on the CPU before the first update)."""
@@ -131,9 +130,7 @@ class _Confusion:
     def _adopt(self, M: torch.Tensor):
         """Read the (K+1) * K int64 counts `M` that someone else owns and updates (ClipValidation) instead of counts of its own:
         no copy, every read of this object sees M's current values."""
-        k = self.num_classes
-        if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
-            raise CavpError(f"_adopt: a dense int64 tensor of {(k + 1) * k} counts required")
+        ops._check_counts(M, self.num_classes, "_adopt")
         self._M = M.view(-1)
         return self
 
@@ -408,16 +405,8 @@ class ClipValidation:
         for t in (pred, labels, count):
             if t is not None and t.device != self.device:
                 raise CavpError(f"ClipValidation lives on {self.device}, got a tensor on {t.device}")
-        lib = _lib.load()
-        st = C.c_void_p(ops._stream())
-        i64 = 1 if count is not None and count.dtype == torch.int64 else 0
-        k = self.num_classes
-        _lib.check(lib.cavp_clipval_frame_counts(ops._ptr(pred.detach()), 1 if is_mask else 0, ops._ptr(labels), ops._ptr(count), i64,
-                                                 B, T, c, HW, k, self.ignore_index, ops._ptr(self._hist), ops._ptr(self._conf),
-                                                 ops._ptr(self._state), st), f"cavp_clipval_frame_counts B{B} T{T} C{c} HW{HW} K{k}")
-        _lib.check(lib.cavp_clipval_combine(ops._ptr(self._hist), ops._ptr(self._conf), ops._ptr(self._flags), ops._ptr(count), i64,
-                                            B, T, k, self.min_count, self.min_values, ops._ptr(self._counts), ops._ptr(self._frames),
-                                            ops._ptr(self._state), st), f"cavp_clipval_combine B{B} T{T} K{k}")
+        ops.clipval_update(pred.detach(), is_mask, labels, count, B, T, c, HW, self.num_classes, self.ignore_index, self.min_count,
+                           self.min_values, self._hist, self._conf, self._flags, self._counts, self._frames, self._state)
 
     # ---- reading -----------------------------------------------------------------------------------------------------------
     def counts(self) -> torch.Tensor:

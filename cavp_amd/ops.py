@@ -477,6 +477,17 @@ def _metric_code(t: torch.Tensor, what: str) -> int:
         raise _lib.CavpError(f"{what}: dtype {t.dtype} unsupported (float32 or int64)") from None
 
 
+def _check_labels(labels: torch.Tensor, shape, what: str) -> None:
+    if tuple(labels.shape) != tuple(shape) or not labels.is_contiguous():
+        raise _lib.CavpError(f"{what}: dense labels of shape {tuple(shape)} required, got {tuple(labels.shape)}")
+
+
+def _check_counts(M: torch.Tensor, k: int, what: str) -> None:
+    """M holds the (K+1) x K confusion counts the kernels add into."""
+    if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
+        raise _lib.CavpError(f"{what}: M must be a dense int64 tensor of (K+1)*K counts")
+
+
 def seg_confusion(logits: torch.Tensor, labels: torch.Tensor, num_classes: int, ignore: int, M: torch.Tensor) -> torch.Tensor:
     """M[(K+1) * K] (int64, read as u64 counts) += the confusion counts of argmax_c(logits) against labels (include/cavp_hip.h,
     cavp_seg_confusion_nchw).  logits: dense f32 [N, C, H, W]; labels: dense [N, H, W], int64 or float32 holding integers
@@ -485,13 +496,11 @@ def seg_confusion(logits: torch.Tensor, labels: torch.Tensor, num_classes: int, 
     if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
         raise _lib.CavpError(f"seg_confusion: dense float32 [N, C, H, W] logits required, got {logits.dtype} {tuple(logits.shape)}")
     n, c, h, w = logits.shape
-    if tuple(labels.shape) != (n, h, w) or not labels.is_contiguous():
-        raise _lib.CavpError(f"seg_confusion: dense labels of shape {(n, h, w)} required, got {tuple(labels.shape)}")
+    _check_labels(labels, (n, h, w), "seg_confusion")
     k = int(num_classes)
     if k < c:
         raise _lib.CavpError(f"seg_confusion: num_classes {k} < logit channels {c}")
-    if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
-        raise _lib.CavpError("seg_confusion: M must be a dense int64 tensor of (K+1)*K counts")
+    _check_counts(M, k, "seg_confusion")
     st = _lib.load().cavp_seg_confusion_nchw(_ptr(logits), _ptr(labels), _metric_code(labels, "seg_confusion"), n, c, h * w, k,
                                              int(ignore), _ptr(M), C.c_void_p(_stream()))
     _lib.check(st, f"cavp_seg_confusion_nchw N{n} C{c} HW{h * w} K{k}")
@@ -585,15 +594,28 @@ def seg_predict(lo: torch.Tensor, out_hw, *, mask: Optional[torch.Tensor] = None
         if num_classes is None:
             raise _lib.CavpError("seg_predict: num_classes is required with M")
         k = int(num_classes)
-        if tuple(labels.shape) != (n, ho, wo) or not labels.is_contiguous():
-            raise _lib.CavpError(f"seg_predict: dense labels of shape {(n, ho, wo)} required, got {tuple(labels.shape)}")
+        _check_labels(labels, (n, ho, wo), "seg_predict")
         if k < c:
             raise _lib.CavpError(f"seg_predict: num_classes {k} < logit channels {c}")
-        if M.dtype != torch.int64 or not M.is_contiguous() or M.numel() != (k + 1) * k:
-            raise _lib.CavpError("seg_predict: M must be a dense int64 tensor of (K+1)*K counts")
+        _check_counts(M, k, "seg_predict")
         code = _metric_code(labels, "seg_predict")
     st = _lib.load().cavp_seg_predict_nhwc(dtype_code(lo.dtype), _ptr(lo), n, hi, wi, c, ldx, ho, wo, int(align_corners), _ptr(mask),
                                            _ptr(prob), int(channel), _ptr(labels), code, k, int(ignore), _ptr(M),
                                            C.c_void_p(_stream()))
     _lib.check(st, f"cavp_seg_predict_nhwc N{n} {hi}x{wi}->{ho}x{wo} C{c} K{k}")
     return mask, prob, M
+
+
+def clipval_update(pred: torch.Tensor, is_mask: bool, labels: torch.Tensor, count: Optional[torch.Tensor], B: int, T: int, c: int, hw: int,
+                   k: int, ignore: int, min_count: int, min_values: int, hist: torch.Tensor, conf: torch.Tensor, flags: torch.Tensor,
+                   counts: torch.Tensor, frames: torch.Tensor, state: torch.Tensor) -> None:
+    """One ClipValidation update of inputs that metrics.ClipValidation has checked (include/cavp_hip.h, cavp_clipval_frame_counts
+    and cavp_clipval_combine): the frames' label histograms and confusion counts into the scratch hist / conf, then the flags
+    and the adds into counts [2, K+1, K], frames [2] and state [4]."""
+    lib, st = _lib.load(), C.c_void_p(_stream())
+    i64 = 1 if count is not None and count.dtype == torch.int64 else 0
+    _lib.check(lib.cavp_clipval_frame_counts(_ptr(pred), 1 if is_mask else 0, _ptr(labels), _ptr(count), i64, B, T, c, hw, k, ignore,
+                                             _ptr(hist), _ptr(conf), _ptr(state), st),
+               f"cavp_clipval_frame_counts B{B} T{T} C{c} HW{hw} K{k}")
+    _lib.check(lib.cavp_clipval_combine(_ptr(hist), _ptr(conf), _ptr(flags), _ptr(count), i64, B, T, k, min_count, min_values,
+                                        _ptr(counts), _ptr(frames), _ptr(state), st), f"cavp_clipval_combine B{B} T{T} K{k}")

@@ -109,6 +109,10 @@ def test_sweep(hw, BT, K):
     counts = [[1], [0]] if B == 1 else [[T, 0, 2], [1, T, T - 1]]
     runs = [(logits, counts[0], torch.int32), (mask, counts[0], torch.int64), (mask, counts[1], torch.int32),
             (logits, counts[1], torch.int64), (mask, None, None)]
+    if (H * W) % 4 == 0:   # whole quads, but the mask starts one byte past a 4-byte boundary: the element path of the mask input
+        shifted = torch.empty(mask.numel() + 1, dtype=torch.uint8, device=DEV)[1:].view_as(mask).copy_(mask)
+        assert shifted.is_contiguous() and shifted.data_ptr() % 4 == 1
+        runs.append((shifted, None, None))
     for pred, count, dtype in runs:
         ref = R.clip_validation(pred.cpu(), labels, count, K)
         cv = MT.ClipValidation(num_classes=K, max_frames=B * T, device=DEV)
