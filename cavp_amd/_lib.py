@@ -184,6 +184,10 @@ PROTOTYPES = {
     # ---- clip validation: frames routed into the ALL and the multi-source confusion matrix (added to ABI 16) ----
     "cavp_clipval_frame_counts": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     "cavp_clipval_combine": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # ---- video validation: per-video J and F of the AVSBench object sets (added to ABI 16) ----
+    "cavp_videoval_frame_stats": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    "cavp_videoval_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -17,6 +17,9 @@
 //                  suffix sums of it are Eval_Fmeasure's y_temp.sum() and tp for every threshold.
 //   clipval:       the frames of a batch of clips routed into an ALL and a multi-source confusion matrix: per frame a 256-bin label
 //                  histogram and the seg_confusion counts in scratch, then a flag per frame from its histogram and the adds.
+//   videoval:      the frames of a batch of videos in one pass: per frame the mask_iou_stats sums and the fmeasure_hist histograms
+//                  in scratch, the seg_confusion counts into the global matrix; then one workgroup per video finishes J and F in
+//                  float32 (the one float tail that runs on the device: per-video scores are stored results).
 #include "common.h"
 #include "host_util.h"
 
@@ -217,6 +220,16 @@ __global__ __launch_bounds__(kThreads) void mask_iou_stats_kernel(const TP* __re
   }
 }
 
+// #{i : th[i] <= p} on the ascending table (a NaN lands in bin 0: th <= p is false for all)
+__device__ __forceinline__ int threshold_bin(const float* s_th, int pr_num, float p) {
+  int lo = 0, hi = pr_num;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s_th[mid] <= p) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 template <typename TG>
 __global__ __launch_bounds__(kThreads) void fmeasure_hist_kernel(const float* __restrict__ src, long long src_ld, const TG* __restrict__ gt,
                                                                 const float* __restrict__ th, int C, int channel, long long HW,
@@ -241,13 +254,9 @@ __global__ __launch_bounds__(kThreads) void fmeasure_hist_kernel(const float* __
       for (int c = 0; c < C; ++c) s += expf(x[c * HW] - m);
       p = expf(x[channel * HW] - m) / s;
     }
-    int lo = 0, hi = pr_num;   // #{i : th[i] <= p} on the ascending table (a NaN lands in bin 0: p >= th is false for all)
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (s_th[mid] <= p) lo = mid + 1; else hi = mid;
-    }
-    atomicAdd(h0 + lo, 1u);
-    if (G[i] != (TG)0) atomicAdd(h1 + lo, 1u);
+    const int bin = threshold_bin(s_th, pr_num, p);
+    atomicAdd(h0 + bin, 1u);
+    if (G[i] != (TG)0) atomicAdd(h1 + bin, 1u);
   }
   lds_counts_flush(h0, 2 * (pr_num + 1), hist + n * 2 * (pr_num + 1));
 }
@@ -543,6 +552,301 @@ __global__ __launch_bounds__(kThreads) void clipval_combine_kernel(unsigned* __r
   if (ms) atomicAdd(counts + nbins + i, ms);
 }
 
+// ---- video validation: per-video J (mask IoU) and F (best F-measure) of the AVSBench object sets ----------------------------------
+// frame_kernel: per participating frame, from one read of the prediction, the four mask_iou_stats sums, the two fmeasure_hist
+//               histograms (per-frame scratch) and the seg_confusion counts (straight into the global matrix).
+// combine_kernel: one workgroup per video: the float32 tail of mask_iou and Eval_Fmeasure, J and F into the video's slot, the
+//               scratch cleared again, the slot base advanced by the last workgroup to finish.
+constexpr int kSoftmaxRegC = 4;   // logits of at most this many channels are held in registers between argmax and softmax
+enum { kVvBadLabel = 0, kVvBadMask = 1, kVvBadCount = 2, kVvDropped = 3, kVvVideos = 4, kVvTicket = 5 };   // state words
+
+// idx[j]: quad_argmax_nchw's argmax; pr[j]: fmeasure_hist_kernel's softmax of channel `channel` (max-subtracted, the channels
+// summed in ascending order, IEEE division) of pixel j of the quad at src.
+template <bool kVec>
+__device__ __forceinline__ void quad_argmax_softmax_nchw(const float* src, int C, long long HW, int np, int channel, int idx[4],
+                                                         float pr[4]) {
+  if (C <= kSoftmaxRegC) {
+    float v[kSoftmaxRegC][4];
+#pragma unroll
+    for (int c = 0; c < kSoftmaxRegC; ++c) {
+      if (c < C) load_quad<float, kVec>(src + c * HW, np, v[c]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float best = v[0][j], m = v[0][j];
+      idx[j] = 0;
+#pragma unroll
+      for (int c = 1; c < kSoftmaxRegC; ++c) {
+        if (c < C) {
+          argmax_step(v[c][j], c, best, idx[j]);
+          m = fmaxf(m, v[c][j]);
+        }
+      }
+      float s = 0.f, xc = 0.f;
+#pragma unroll
+      for (int c = 0; c < kSoftmaxRegC; ++c) {
+        if (c < C) {
+          s += expf(v[c][j] - m);
+          if (c == channel) xc = v[c][j];
+        }
+      }
+      pr[j] = expf(xc - m) / s;
+    }
+  } else {
+    quad_argmax_nchw<kVec>(src, C, HW, np, idx);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      pr[j] = 0.f;
+      if (j < np) {
+        const float* x = src + j;
+        float m = x[0];
+        for (int c = 1; c < C; ++c) m = fmaxf(m, x[c * HW]);
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) s += expf(x[c * HW] - m);
+        pr[j] = expf(x[channel * HW] - m) / s;
+      }
+    }
+  }
+}
+
+// grid (chunks, B*T): a workgroup belongs to one frame.  One thread = 4 consecutive pixels; block-uniform trip count (add_bins
+// ballots).  LDS: [pr_num] thresholds, [2][pr_num+1] histograms, then (kLds) the workgroup's (K+1)*K confusion counts.  The
+// histogram bin is bounded by the search (<= pr_num), the confusion bin by p < K (a mask byte >= K sets none).
+template <bool kMask, bool kVec, bool kLds>
+__global__ __launch_bounds__(kThreads) void videoval_frame_kernel(const void* __restrict__ pred, const float* __restrict__ prob,
+                                                                 const long long* __restrict__ labels, const void* __restrict__ count,
+                                                                 int count_i64, int T, int C, int channel, long long HW, int K,
+                                                                 long long ignore, const float* __restrict__ th, int pr_num,
+                                                                 unsigned long long* __restrict__ stats, unsigned* __restrict__ hist,
+                                                                 unsigned long long* __restrict__ M, unsigned long long* __restrict__ state) {
+  extern __shared__ unsigned lds[];
+  const int n = blockIdx.y, b = n / T, t = n - b * T;
+  if (t >= clip_count(count, count_i64, b, T)) return;   // workgroup-uniform: the frame is not read
+  const int nbins = (K + 1) * K, nh = 2 * (pr_num + 1);
+  float* s_th = (float*)lds;
+  unsigned* h0 = lds + pr_num;
+  unsigned* h1 = h0 + pr_num + 1;
+  unsigned* lconf = h0 + nh;
+  for (int i = threadIdx.x; i < pr_num; i += kThreads) s_th[i] = th[i];
+  lds_counts_clear(h0, nh + (kLds ? nbins : 0));   // its barrier covers s_th too
+  const long long* lab_n = labels + (long long)n * HW;
+  const long long nq = (HW + 3) >> 2;
+  long long s[4] = {0, 0, 0, 0};
+  unsigned bad_label = 0, bad_mask = 0;
+  for (long long base = (long long)blockIdx.x * kThreads; base < nq; base += (long long)gridDim.x * kThreads) {
+    const long long q = base + threadIdx.x;
+    int cb[4] = {-1, -1, -1, -1};
+    if (q < nq) {
+      const long long p0 = q * 4;
+      const int np = quad_pixels<kVec>(HW - p0);
+      long long tv[4];
+      load_quad<long long, kVec>(lab_n + p0, np, tv);
+      int p[4];
+      float pr[4];
+      if (kMask) {
+        unsigned char m[4];
+        load_quad<unsigned char, kVec>((const unsigned char*)pred + (long long)n * HW + p0, np, m);
+        load_quad<float, kVec>(prob + (long long)n * HW + p0, np, pr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = m[j];
+      } else {
+        quad_argmax_softmax_nchw<kVec>((const float*)pred + (long long)n * C * HW + p0, C, HW, np, channel, p, pr);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j >= np) continue;
+        const long long v = tv[j], pj = p[j];
+        const int bin = threshold_bin(s_th, pr_num, pr[j]);
+        atomicAdd(h0 + bin, 1u);
+        if (v != 0) atomicAdd(h1 + bin, 1u);
+        s[0] += pj * v;
+        s[1] += pj > v ? pj : v;
+        s[2] += (1 - v) * (1 - pj);
+        s[3] += v;
+        if (v != 0 && v != 1 && v != ignore) ++bad_label;
+        if (kMask && p[j] >= K) ++bad_mask;
+        else cb[j] = conf_bin(v, p[j], K, ignore);
+      }
+    }
+    add_bins<kLds>(cb, lconf, M);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    long long v = s[k];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(stats + (size_t)n * 4 + k, (unsigned long long)v);   // two's complement: a signed sum
+  }
+  if (bad_label) atomicAdd(state + kVvBadLabel, (unsigned long long)bad_label);
+  if (bad_mask) atomicAdd(state + kVvBadMask, (unsigned long long)bad_mask);
+  lds_counts_flush(h0, nh, hist + (size_t)n * nh);
+  if (kLds) lds_counts_flush(lconf, nbins, M);
+}
+
+// sum over the workgroup of two ints per thread; part: [2][kThreads / 64] in LDS
+__device__ __forceinline__ void block_sum2(int& a, int& b, int (*part)[kThreads / 64]) {
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = a; part[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  a = b = 0;
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) { a += part[0][w]; b += part[1][w]; }
+}
+
+constexpr int kWaves = kThreads / 64;
+
+// LDS words of a combine workgroup: a [2][pr_num+1] histogram per wave, kWaves + 1 rows of [pr_num] floats, [kThreads] floats
+__host__ __device__ constexpr size_t videoval_combine_words(int pr_num) {
+  return (size_t)kWaves * 2 * (pr_num + 1) + (size_t)(kWaves + 1) * pr_num + kThreads;
+}
+
+// grid B: one workgroup = one video.  The frames are taken kWaves at a time, one wave per frame: the wave turns its frame's two
+// histograms into suffix sums in LDS (a lane sums its run of bins, the lane totals are scanned with shuffles) and writes f of every
+// threshold; then the workgroup adds the group's f rows to the running sums in ascending frame order.  Every float step is one
+// IEEE operation (__f*_rn: the build contracts a * b + c).
+__global__ __launch_bounds__(kThreads) void videoval_combine_kernel(unsigned long long* __restrict__ stats, unsigned* __restrict__ hist,
+                                                                   const void* __restrict__ count, int count_i64, int B, int T,
+                                                                   long long HW, int pr_num, int max_videos, float* __restrict__ J,
+                                                                   float* __restrict__ F, unsigned long long* __restrict__ state) {
+  extern __shared__ unsigned lds[];
+  __shared__ int part[2][kWaves];
+  __shared__ float wave_max[kWaves];
+  __shared__ int valid[kWaves];
+  const int nb = pr_num + 1, nh = 2 * nb;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned* cnts = lds + (size_t)wave * nh;         // this wave's frame: [2][nb] counts, then their suffix sums
+  float* fbuf = (float*)(lds + (size_t)kWaves * nh);   // [kWaves][pr_num]: f of the group's frames
+  float* acc = fbuf + (size_t)kWaves * pr_num;      // [pr_num]: the sums of f over the frames kept
+  float* iou = acc + pr_num;                        // [kThreads]: overlap / union of a run of frames
+  const int b = blockIdx.x;
+  const int cnt = clip_count(count, count_i64, b, T);
+  // videos with frames in front of this one, and in the whole call
+  int before = b, videos = B;
+  if (count) {
+    before = videos = 0;
+    for (int i = threadIdx.x; i < B; i += kThreads) {
+      const int has = clip_count(count, count_i64, i, T) > 0 ? 1 : 0;
+      videos += has;
+      if (i < b) before += has;
+    }
+    block_sum2(before, videos, part);
+  }
+  if (cnt > 0) {   // workgroup-uniform
+    // J: the frames' quotients side by side, then added by one thread in ascending order
+    float sum = 0.f;
+    for (int t0 = 0; t0 < cnt; t0 += kThreads) {
+      const int t = t0 + threadIdx.x;
+      if (t < cnt) {
+        const unsigned long long* s = stats + ((size_t)b * T + t) * 4;
+        long long overlap = (long long)s[0], uni = (long long)s[1];
+        if (s[3] == 0ull) { overlap = (long long)s[2]; uni = HW; }   // mask_iou's empty target: the background overlap over all pixels
+        iou[threadIdx.x] = __fdiv_rn((float)overlap, __fadd_rn((float)uni, 1e-7f));
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const int n = cnt - t0 < kThreads ? cnt - t0 : kThreads;
+        for (int k = 0; k < n; ++k) sum = __fadd_rn(sum, iou[k]);
+      }
+      __syncthreads();
+    }
+    // F
+    for (int i = threadIdx.x; i < pr_num; i += kThreads) acc[i] = 0.f;
+    int kept = 0;
+    const int run = (nb + 63) >> 6;   // bins per lane
+    for (int t0 = 0; t0 < cnt; t0 += kWaves) {
+      const bool mine = t0 + wave < cnt;   // wave-uniform
+      if (mine) {
+        const unsigned* h = hist + ((size_t)b * T + t0 + wave) * nh;
+        for (int i = lane; i < nh; i += 64) cnts[i] = h[i];
+      }
+      __syncthreads();
+      if (mine) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {   // cnts[a][k] = sum over k' >= k
+          unsigned* c = cnts + a * nb;
+          const int lo = lane * run < nb ? lane * run : nb, hi = lo + run < nb ? lo + run : nb;
+          unsigned own = 0;
+          for (int k = lo; k < hi; ++k) own += c[k];
+          unsigned suf = own;   // the total of this lane and the lanes above it
+          for (int o = 1; o < 64; o <<= 1) {
+            const unsigned v = __shfl_down(suf, o, 64);
+            if (lane + o < 64) suf += v;
+          }
+          unsigned above = suf - own;
+          for (int k = hi - 1; k >= lo; --k) {
+            above += c[k];
+            c[k] = above;
+          }
+        }
+      }
+      __syncthreads();
+      if (mine) {
+        const unsigned* all = cnts;
+        const unsigned* pos = cnts + nb;
+        if (lane == 0) valid[wave] = pos[0] != 0u;   // an all-zero gt: the frame is skipped
+        if (pos[0] != 0u) {
+          const float ysum = __fadd_rn((float)pos[0], 1e-20f);
+          for (int i = lane; i < pr_num; i += 64) {
+            const float tp = (float)pos[i + 1];
+            const float prec = __fdiv_rn(tp, __fadd_rn((float)all[i + 1], 1e-20f));
+            const float recall = __fdiv_rn(tp, ysum);
+            float f = __fdiv_rn(__fmul_rn(__fmul_rn((float)(1.0 + 0.3), prec), recall), __fadd_rn(__fmul_rn(0.3f, prec), recall));
+            if (f != f) f = 0.f;
+            fbuf[(size_t)wave * pr_num + i] = f;
+          }
+        }
+      }
+      __syncthreads();
+      const int frames = cnt - t0 < kWaves ? cnt - t0 : kWaves;
+      for (int w = 0; w < frames; ++w) {   // ascending t
+        if (!valid[w]) continue;           // workgroup-uniform
+        ++kept;
+        for (int i = threadIdx.x; i < pr_num; i += kThreads) acc[i] = __fadd_rn(acc[i], fbuf[(size_t)w * pr_num + i]);   // acc[i] is this thread's
+      }
+      __syncthreads();   // fbuf, valid and cnts are free again
+    }
+    float best = 0.f;   // every score is >= 0
+    for (int i = threadIdx.x; i < pr_num; i += kThreads) {
+      const float score = kept > 0 ? __fdiv_rn(acc[i], (float)kept) : 0.f;
+      best = fmaxf(best, score);
+    }
+    for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+    if (lane == 0) wave_max[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int w = 1; w < kWaves; ++w) best = fmaxf(best, wave_max[w]);
+      // the slot base is only advanced by the last workgroup of this launch, after every workgroup has read it
+      const unsigned long long slot = atomicAdd(state + kVvVideos, 0ull) + (unsigned long long)before;
+      if (slot < (unsigned long long)max_videos) {
+        J[slot] = __fdiv_rn(sum, (float)cnt);
+        F[slot] = best;
+      } else {
+        atomicAdd(state + kVvDropped, 1ull);
+      }
+    }
+    // every read of this video's scratch lies before the last barrier above: clear it
+    unsigned long long* s = stats + (size_t)b * T * 4;
+    for (int i = threadIdx.x; i < cnt * 4; i += kThreads) s[i] = 0ull;
+    unsigned* h = hist + (size_t)b * T * nh;
+    for (long long i = threadIdx.x; i < (long long)cnt * nh; i += kThreads) h[i] = 0u;
+  }
+  if (threadIdx.x == 0) {
+    if (count) {
+      const long long c = clip_count_raw(count, count_i64, b);
+      if (c < 0 || c > T) atomicAdd(state + kVvBadCount, 1ull);
+    }
+    __threadfence();
+    if (atomicAdd(state + kVvTicket, 1ull) == (unsigned long long)(B - 1)) {   // the last workgroup of the launch
+      atomicAdd(state + kVvVideos, (unsigned long long)videos);
+      atomicExch(state + kVvTicket, 0ull);
+    }
+  }
+}
+
 // ---- host side: the checks the entry points share, run-time arguments -> template arguments -------------------------------------
 bool label_ok(int code) { return code == CAVP_I64 || code == CAVP_F32; }
 bool classes_ok(int K, int C) { return K >= C && K <= CAVP_METRICS_MAX_CLASSES; }
@@ -701,5 +1005,48 @@ extern "C" int cavp_clipval_combine(uint32_t* hist, uint32_t* conf, uint32_t* fl
                                                (unsigned long long*)frames, (unsigned long long*)state);
   const dim3 grid((nbins + kThreads - 1) / kThreads, (N + kCombineFrames - 1) / kCombineFrames);
   clipval_combine_kernel<<<grid, kThreads, 0, s>>>(conf, flags, N, nbins, (unsigned long long*)counts);
+  CHECK_LAUNCH();
+}
+
+// LDS words of a videoval frame workgroup: thresholds, both histograms and (lds) the confusion counts
+static size_t videoval_frame_words(int pr_num, int K, bool lds) { return (size_t)pr_num + 2 * ((size_t)pr_num + 1) + (lds ? (size_t)(K + 1) * K : 0); }
+
+extern "C" int cavp_videoval_frame_stats(const void* pred, int32_t pred_is_mask, const float* prob, const int64_t* labels, const void* count,
+                                         int32_t count_i64, int32_t B, int32_t T, int32_t C, int32_t channel, int64_t HW, int32_t K,
+                                         int64_t ignore, const float* thresholds, int32_t pr_num, int64_t* stats, uint32_t* hist,
+                                         uint64_t* M, int64_t* state, void* stream) {
+  if (!pred || !labels || !thresholds || !stats || !hist || !M || !state || B <= 0 || T <= 0 || HW <= 0 || K <= 0 || pr_num <= 0)
+    return CAVP_ERR_BAD_ARG;
+  if (pred_is_mask ? !prob : (C < 2 || channel < 0 || channel >= C)) return CAVP_ERR_BAD_ARG;
+  if ((long long)B * T > 65535 || HW > 0x7fffffffLL || pr_num > CAVP_VIDEOVAL_MAX_THRESHOLDS) return CAVP_ERR_UNSUPPORTED;   // grid.y; u32 counts
+  if (!classes_ok(K, pred_is_mask ? 0 : C)) return CAVP_ERR_UNSUPPORTED;   // a mask has no channels
+  if (((uintptr_t)labels & 7) || ((uintptr_t)stats & 7) || ((uintptr_t)hist & 3) || ((uintptr_t)M & 7) || ((uintptr_t)state & 7) ||
+      ((uintptr_t)thresholds & 3) || (pred_is_mask ? ((uintptr_t)prob & 3) != 0 : ((uintptr_t)pred & 3) != 0) ||
+      !aligned_for(count, count_i64 != 0))
+    return CAVP_ERR_ALIGN;
+  const bool vec = (HW & 3) == 0 && al16(labels) && (pred_is_mask ? ((uintptr_t)pred & 3) == 0 && al16(prob) : al16(pred));
+  // the confusion counts are privatised when they fit the default 64 KiB beside the thresholds and the histograms (K <= 124 at 255)
+  const bool lds = counts_fit_lds(K) && videoval_frame_words(pr_num, K, true) <= (size_t)kLdsBins;
+  // 2 quads per thread, as clipval_frame_kernel: 25 workgroups per frame at 224^2
+  const dim3 grid(chunks_for((HW + 3) >> 2, 2 * kThreads, 64), B * T);
+  const size_t shm = videoval_frame_words(pr_num, K, lds) * sizeof(unsigned);
+  hipStream_t s = (hipStream_t)stream;
+  cavp_dispatch_bool(pred_is_mask != 0, [&](auto m) { cavp_dispatch_bool(vec, [&](auto v) { cavp_dispatch_bool(lds, [&](auto l) {
+    videoval_frame_kernel<decltype(m)::value, decltype(v)::value, decltype(l)::value><<<grid, kThreads, shm, s>>>(
+        pred, prob, (const long long*)labels, count, count_i64, T, C, channel, HW, K, ignore, thresholds, pr_num,
+        (unsigned long long*)stats, hist, (unsigned long long*)M, (unsigned long long*)state); }); }); });
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_videoval_combine(int64_t* stats, uint32_t* hist, const void* count, int32_t count_i64, int32_t B, int32_t T, int64_t HW,
+                                     int32_t pr_num, int32_t max_videos, float* J, float* F, int64_t* state, void* stream) {
+  if (!stats || !hist || !J || !F || !state || B <= 0 || T <= 0 || HW <= 0 || pr_num <= 0 || max_videos <= 0) return CAVP_ERR_BAD_ARG;
+  if ((long long)B * T > 65535 || HW > 0x7fffffffLL || pr_num > CAVP_VIDEOVAL_MAX_THRESHOLDS) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)stats & 7) || ((uintptr_t)hist & 3) || ((uintptr_t)J & 3) || ((uintptr_t)F & 3) || ((uintptr_t)state & 7) ||
+      !aligned_for(count, count_i64 != 0))
+    return CAVP_ERR_ALIGN;
+  const size_t shm = videoval_combine_words(pr_num) * sizeof(unsigned);
+  videoval_combine_kernel<<<B, kThreads, shm, (hipStream_t)stream>>>((unsigned long long*)stats, hist, count, count_i64, B, T, HW, pr_num,
+                                                                      max_videos, J, F, (unsigned long long*)state);
   CHECK_LAUNCH();
 }

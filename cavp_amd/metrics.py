@@ -22,7 +22,8 @@ logits are never written), `update(x, y)` (no host sync; no allocation after the
 forward), `reset()`, `counts()` (the device-side (K+1) x K confusion counts) and `fmeasure_curve(...)` (the score curve as a
 device tensor, without `.item()`), and `ClipValidation`: the validation loop of the AVSS trainers (trainer_cavp_avss_image.py:295-349)
 for whole batches of clips - every frame counted into an ALL matrix and, when its own label histogram says "multi-source", into an
-MS matrix as well, decided on the device."""
+MS matrix as well, decided on the device; and `VideoValidation`: the validation loop of the AVSBench object trainer
+(trainer_cavp_avs_obj.py:292-363) - per-video J (mask_iou) and F (Eval_Fmeasure) of whole batches of videos, finished on the device."""
 from __future__ import annotations
 
 import numpy
@@ -33,7 +34,8 @@ from ._lib import CavpError
 from .train_ops import zero_ as _zero_
 from .train_ops import zeros as _zeros
 
-__all__ = ["MIoU", "ForegroundDetect", "get_performance", "mask_iou", "Eval_Fmeasure", "fmeasure_curve", "ClipValidation"]
+__all__ = ["MIoU", "ForegroundDetect", "get_performance", "mask_iou", "Eval_Fmeasure", "fmeasure_curve", "ClipValidation",
+           "VideoValidation"]
 
 
 def get_performance(miou_measure_in, fg_measure_in, class_list=None):
@@ -449,3 +451,252 @@ class ClipValidation:
             _zero_(self._state)
             raise CavpError(f"ClipValidation: {bad[0]} label(s) >= 256, {bad[1]} mask value(s) >= {self.num_classes}, "
                             f"{bad[2]} count(s) outside [0, T] since the last check")
+
+
+MAX_VIDEOS = 1 << 20               # per-video slots one VideoValidation may ask for
+
+
+class VideoValidation:
+    """The validation loop of the AVSBench object trainer (S4 / MS3: trainer_cavp_avs_obj.py:292-363) for whole batches of videos,
+    without the host:
+
+        vv = VideoValidation(num_classes=2, ignore_index=255, pr_num=255, channel=1, max_frames=320, max_videos=4096)
+        vv.update(model(image, audio, eval_mode=True)[0], labels, count)        # or vv.update_lowres(model.predict_lowres(...), ...)
+        (avs_miou, avs_f), (miou, acc, fdr, f1, f03) = vv.results()
+
+    logits: dense float32 [B*T, C, H, W], 2 <= C <= num_classes.  labels: dense int64 [B, T, H, W] (or [N, H, W] with count=None:
+    one video); never written.  count: device int32 / int64 [B], the reference's mask_num per video: frame t of video b takes part
+    iff t < count[b] (None: every frame); a frame that takes no part is not read by the metric kernels.  The reference defines this
+    loop only for mask_num == T (its mask_iou asserts equal shapes of the mask_num predictions and the T labels); count[b] < T
+    means the reference applied to the first count[b] frames of video b.
+
+    Per video with at least one frame, in float32 with the reference's operations and order: J = mask_iou(argmax(logits), labels)
+    (an empty target scores its background overlap over all pixels) and F = Eval_Fmeasure(softmax(logits)[:, channel], labels) (the
+    best of `pr_num` thresholds; frames with an all-zero gt are skipped, a video of such frames scores 0; gt = labels != 0), stored
+    in the video's slot: batch order within an update, call order across updates.  Every participating frame also adds its
+    confusion counts (the (K+1) x K bin rule of MIoU / ForegroundDetect) to one matrix, which `miou` and `fg` read (no copies).
+
+    update() is two launches and update_lowres() three (csrc/metrics.hip); neither synchronises, neither allocates
+    after its first call, so both can be captured in a hipGraph with the eval forward (run one eager call first).  The counts are
+    integer adds and the float tail runs in a fixed order: the results do not depend on arrival order.  A count[b] outside [0, T]
+    is clamped, a video beyond `max_videos` is not stored, a label outside {0, 1, ignore_index} is counted by the rules above all
+    the same; each is counted on the device, and check() raises if there were any."""
+
+    def __init__(self, num_classes: int = 2, ignore_index=255, pr_num: int = 255, channel: int = 1, max_frames: int = 320,
+                 max_videos: int = 4096, device=None):
+        k = int(num_classes)
+        if not 2 <= k <= MAX_CLASSES:
+            raise CavpError(f"VideoValidation: 2 <= num_classes <= {MAX_CLASSES}, got {num_classes}")
+        if not 1 <= int(pr_num) <= ops.VIDEOVAL_MAX_THRESHOLDS:
+            raise CavpError(f"VideoValidation: 1 <= pr_num <= {ops.VIDEOVAL_MAX_THRESHOLDS}, got {pr_num}")
+        if not 0 <= int(channel) < k:
+            raise CavpError(f"VideoValidation: 0 <= channel < num_classes, got {channel}")
+        if not 1 <= int(max_frames) <= MAX_CLIP_FRAMES:
+            raise CavpError(f"VideoValidation: 1 <= max_frames <= {MAX_CLIP_FRAMES}")
+        if not 1 <= int(max_videos) <= MAX_VIDEOS:
+            raise CavpError(f"VideoValidation: 1 <= max_videos <= {MAX_VIDEOS}")
+        self.num_classes, self.ignore_index = k, ignore_index
+        self.pr_num, self.channel, self.max_frames, self.max_videos = int(pr_num), int(channel), int(max_frames), int(max_videos)
+        self.nbins = (k + 1) * k
+        self._kernel_ignore = -1 if ignore_index is None else int(ignore_index)   # -1 is never counted anyway (t >= 0)
+        self._device = device
+        self._res = None             # device buffers, allocated by the first update (the constructor touches no device)
+        self._lowres = {}            # (N, H, W) -> (mask, prob) of update_lowres
+        self.miou = MIoU(k, ignore_index, 0)
+        self.fg = ForegroundDetect(k, ignore_index, 0)
+
+    # ---- device state ------------------------------------------------------------------------------------------------------
+    def _bind(self, res, stats, hist, th):
+        """Take the device buffers.  res int64 [(K+1)K + 8 + max_videos]: the confusion counts, the state words and J | F (float32)
+        side by side, so that results() is one host read; stats int64 [max_frames, 4] and hist int32 [max_frames, 2, pr_num + 1]
+        (zero at rest); th the threshold table."""
+        mf, mv, nb = self.max_frames, self.max_videos, self.nbins
+        want = ((res, torch.int64, nb + ops.VIDEOVAL_STATE_WORDS + mv), (stats, torch.int64, 4 * mf),
+                (hist, torch.int32, mf * 2 * (self.pr_num + 1)), (th, torch.float32, self.pr_num))
+        for t, dt, numel in want:
+            if t.dtype != dt or t.numel() != numel or not t.is_contiguous() or not t.is_cuda or t.device != res.device:
+                raise CavpError("VideoValidation: device buffers of the wrong dtype, size or device")
+        self.device = res.device
+        self._res, self._stats, self._hist, self._th = res, stats, hist, th
+        self._counts = res[:nb]
+        self._state = res[nb:nb + ops.VIDEOVAL_STATE_WORDS]
+        scores = res[nb + ops.VIDEOVAL_STATE_WORDS:].view(torch.float32)
+        self._J, self._F = scores[:mv], scores[mv:]
+        self.miou._adopt(self._counts)
+        self.fg._adopt(self._counts)
+
+    def _ensure(self):
+        if self._res is None:
+            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            if dev.type != "cuda":
+                raise CavpError("VideoValidation lives on a HIP device (there is no CPU fallback)")
+            if torch.cuda.is_current_stream_capturing():
+                raise CavpError("VideoValidation would allocate during hipGraph capture; run one eager update first")
+            mf = self.max_frames
+            self._bind(_zeros((self.nbins + ops.VIDEOVAL_STATE_WORDS + self.max_videos,), torch.int64, dev),
+                       _zeros((mf, 4), torch.int64, dev), _zeros((mf, 2, self.pr_num + 1), torch.int32, dev),
+                       thresholds(self.pr_num, dev))
+
+    # ---- the updates -------------------------------------------------------------------------------------------------------
+    def _check_labels(self, labels, count):
+        """(B, T, H, W) of the labels and the optional count."""
+        E = CavpError
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() not in (3, 4):
+            raise E(f"VideoValidation: labels must be an int64 tensor [B, T, H, W] (or [N, H, W] without count), got "
+                    f"{getattr(labels, 'dtype', type(labels))} {tuple(getattr(labels, 'shape', ()))}")
+        if labels.dim() == 3 and count is not None:
+            raise E("VideoValidation: count needs labels [B, T, H, W]")
+        B, T = (labels.shape[0], labels.shape[1]) if labels.dim() == 4 else (1, labels.shape[0])
+        H, W = labels.shape[-2:]
+        if B * T < 1 or H < 1 or W < 1:
+            raise E("VideoValidation: empty labels are not supported")
+        if B * T > self.max_frames:
+            raise E(f"VideoValidation: {B * T} frames in one update, max_frames = {self.max_frames}")
+        if count is not None:
+            if not isinstance(count, torch.Tensor) or count.dtype not in (torch.int32, torch.int64) or tuple(count.shape) != (B,):
+                raise E(f"VideoValidation: count must be an int32 or int64 tensor of shape ({B},)")
+        if not labels.is_contiguous() or (count is not None and not count.is_contiguous()):
+            raise E("VideoValidation: dense (contiguous) tensors required")
+        return B, T, H, W
+
+    def _on_device(self, *ts):
+        for t in ts:
+            if t is not None and t.device != self.device:
+                raise CavpError(f"VideoValidation lives on {self.device}, got a tensor on {t.device}")
+
+    def _launch(self, pred, prob, labels, count, B, T, hw):
+        ops.videoval_frame_stats(pred, labels, count, T, self.num_classes, self._kernel_ignore, self._th, self._stats, self._hist,
+                                 self._counts, self._state, self.channel, prob)
+        ops.videoval_combine(self._stats, self._hist, count, B, T, hw, self.pr_num, self._J, self._F, self._state)
+
+    def update(self, logits: torch.Tensor, labels: torch.Tensor, count=None) -> None:
+        """Score one batch of videos from full-resolution logits (see the class docstring): two launches, no host sync; graph
+        replays of a captured update() accumulate the same way."""
+        B, T, H, W = self._check_labels(labels, count)
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 4 \
+                or logits.shape[0] != B * T or tuple(logits.shape[2:]) != (H, W):
+            raise CavpError(f"VideoValidation: float32 logits [{B * T}, C, {H}, {W}] required, got "
+                            f"{getattr(logits, 'dtype', type(logits))} {tuple(getattr(logits, 'shape', ()))}")
+        c = logits.shape[1]
+        if not 2 <= c <= self.num_classes:
+            raise CavpError(f"VideoValidation: 2 <= logit channels <= num_classes {self.num_classes}, got {c}")
+        if not self.channel < c:
+            raise CavpError(f"VideoValidation: channel {self.channel} outside the {c} logit channels")
+        if not logits.is_contiguous():
+            raise CavpError("VideoValidation: dense (contiguous) tensors required")
+        ops._need_gpu(logits, labels, count)
+        self._ensure()
+        self._on_device(logits, labels, count)
+        self._launch(logits.detach(), None, labels, count, B, T, H * W)
+
+    def update_lowres(self, lo: torch.Tensor, labels: torch.Tensor, count=None, input_shape=None, align_corners: bool = False) -> None:
+        """update() from the low-resolution logits `lo` (NHWC view [B*T, h, w, C], f32 or bf16: CAVP.predict_lowres): the scores and
+        counts of update(full_res_logits, ...) where full_res_logits is the bilinear upsample of `lo` to `input_shape` (default
+        labels.shape[-2:]), which is never materialised: ops.seg_predict writes the uint8 class mask and the float32 probability
+        plane of all B*T frames, the frame kernel reads those of the participating ones.  Three launches, no host sync, no
+        allocation after the first call with a given (B*T, H, W)."""
+        B, T, H, W = self._check_labels(labels, count)
+        if not isinstance(lo, torch.Tensor) or lo.dim() != 4 or lo.shape[0] != B * T or lo.dtype not in (torch.float32, torch.bfloat16):
+            raise CavpError(f"VideoValidation: low-res logits [{B * T}, h, w, C] (float32 or bfloat16) required, got "
+                            f"{getattr(lo, 'dtype', type(lo))} {tuple(getattr(lo, 'shape', ()))}")
+        shape = (H, W) if input_shape is None else tuple(int(v) for v in input_shape)
+        if shape != (H, W):
+            raise CavpError(f"VideoValidation: input_shape {shape} differs from the labels' {(H, W)}")
+        c = lo.shape[3]
+        if not 2 <= c <= min(self.num_classes, 256):
+            raise CavpError(f"VideoValidation: 2 <= logit channels <= num_classes {self.num_classes} (and 256: a byte mask), got {c}")
+        if not self.channel < c:
+            raise CavpError(f"VideoValidation: channel {self.channel} outside the {c} logit channels")
+        ops._need_gpu(lo, labels, count)
+        self._ensure()
+        self._on_device(lo, labels, count)
+        key = (B * T, H, W)
+        if key not in self._lowres:
+            if torch.cuda.is_current_stream_capturing():
+                raise CavpError("VideoValidation.update_lowres would allocate during hipGraph capture; run one eager call first")
+            self._lowres[key] = (torch.empty(key, dtype=torch.uint8, device=self.device),
+                                 torch.empty(key, dtype=torch.float32, device=self.device))
+        mask, prob = self._lowres[key]
+        ops.seg_predict(lo.detach(), shape, mask=mask, prob=prob, channel=self.channel, align_corners=align_corners)
+        self._launch(mask, prob, labels, count, B, T, H * W)
+
+    # ---- reading -----------------------------------------------------------------------------------------------------------
+    def counts(self) -> torch.Tensor:
+        """The (K+1) x K confusion counts (int64, on the device; zeros on the CPU before the first update)."""
+        k = self.num_classes
+        if self._res is None:
+            return torch.zeros((k + 1, k), dtype=torch.int64)
+        return self._counts.view(k + 1, k)
+
+    def _read(self):
+        """(M int64 [K+1, K], state [8], J float32 [n], F float32 [n]) on the host from ONE copy of the device buffer."""
+        k, nb, mv = self.num_classes, self.nbins, self.max_videos
+        if self._res is None:
+            empty = numpy.zeros(0, dtype=numpy.float32)
+            return numpy.zeros((k + 1, k), dtype=numpy.int64), [0] * ops.VIDEOVAL_STATE_WORDS, empty, empty
+        host = self._res.cpu()
+        state = host[nb:nb + ops.VIDEOVAL_STATE_WORDS].tolist()
+        scores = host[nb + ops.VIDEOVAL_STATE_WORDS:].view(torch.float32).numpy()
+        n = min(state[4], mv)
+        return host[:nb].numpy().reshape(k + 1, k), state, scores[:n], scores[mv:mv + n]
+
+    def videos(self) -> int:
+        """Videos scored so far (those beyond max_videos not included): one host read."""
+        return 0 if self._res is None else min(int(self._state[4].item()), self.max_videos)
+
+    def video_scores(self):
+        """(J, F): float32 [n] device tensors, one entry per scored video in slot order (views; one host read for n)."""
+        if self._res is None:
+            empty = torch.zeros(0, dtype=torch.float32)
+            return empty, empty
+        n = self.videos()
+        return self._J[:n], self._F[:n]
+
+    @staticmethod
+    def _means(J: numpy.ndarray, F: numpy.ndarray):
+        """The reference's two AverageMeter means as Python floats: J (0-d float32 tensors there) summed in float32 in slot order and
+        divided in float32, F (Python floats there) summed and divided in double."""
+        n = J.shape[0]
+        j_mean = numpy.float32(numpy.cumsum(J, dtype=numpy.float32)[-1]) / numpy.float32(n)
+        f_sum = 0.0
+        for v in F.tolist():
+            f_sum += v
+        return float(j_mean), f_sum / n
+
+    def video_means(self):
+        """(mean J, mean F) before rounding, as Python floats: one host read."""
+        _, _, J, F = self._read()
+        if J.shape[0] == 0:
+            raise CavpError("VideoValidation: no video counted yet (the reference divides by zero here)")
+        return self._means(J, F)
+
+    def results(self, class_list=None):
+        """((avs_miou, avs_f), (mIoU, acc, fdr, f1, f0.3)) from ONE host read: the means of the per-video J and F in the reference's
+        AverageMeter arithmetic, each numpy.round(x, 4) (trainer_cavp_avs_obj.py:349-352), and get_performance(miou, fg, class_list)
+        of the frames' confusion counts.  Raises CavpError when no video has been counted (the reference divides by zero)."""
+        M, _, J, F = self._read()
+        if J.shape[0] == 0:
+            raise CavpError("VideoValidation: no video counted yet (the reference divides by zero here)")
+        j_mean, f_mean = self._means(J, F)
+        k = self.num_classes
+        _, _, iou, acc = iou_and_accuracy(M)
+        perf = (*pixel_scores(iou, acc, class_list), *detection_scores(torch.tensor(M[:k].astype(numpy.float64)), class_list))
+        return (numpy.round(j_mean, 4), numpy.round(f_mean, 4)), perf
+
+    def reset(self) -> None:
+        """Forget the videos and zero the confusion counts (the bad-input counters stay until check())."""
+        if self._res is not None:
+            _zero_(self._counts)
+            _zero_(self._state[4:5])
+
+    def check(self) -> None:
+        """Synchronises and raises CavpError if, since the last check, a count was outside [0, T], a video was dropped for
+        max_videos, a label was outside {0, 1, ignore_index} or a mask byte was >= num_classes."""
+        if self._res is None:
+            raise CavpError("check: no VideoValidation update yet")
+        bad = self._state[:4].cpu().tolist()
+        if any(bad):
+            _zero_(self._state[:4])
+            raise CavpError(f"VideoValidation: {bad[0]} label(s) outside {{0, 1, {self.ignore_index}}}, {bad[1]} mask value(s) >= "
+                            f"{self.num_classes}, {bad[2]} count(s) outside [0, T], {bad[3]} video(s) beyond max_videos = "
+                            f"{self.max_videos} since the last check")

@@ -619,3 +619,103 @@ def clipval_update(pred: torch.Tensor, is_mask: bool, labels: torch.Tensor, coun
                f"cavp_clipval_frame_counts B{B} T{T} C{c} HW{hw} K{k}")
     _lib.check(lib.cavp_clipval_combine(_ptr(hist), _ptr(conf), _ptr(flags), _ptr(count), i64, B, T, k, min_count, min_values,
                                         _ptr(counts), _ptr(frames), _ptr(state), st), f"cavp_clipval_combine B{B} T{T} K{k}")
+
+
+VIDEOVAL_MAX_THRESHOLDS = 1024     # CAVP_VIDEOVAL_MAX_THRESHOLDS
+VIDEOVAL_STATE_WORDS = 8           # {labels outside {0, 1, ignore}, mask bytes >= K, bad counts, videos dropped, videos seen, ticket, -, -}
+
+
+def _videoval_scratch(stats: torch.Tensor, hist: torch.Tensor, state: torch.Tensor, n: int, pr: int, what: str) -> None:
+    if not 1 <= pr <= VIDEOVAL_MAX_THRESHOLDS:
+        raise _lib.CavpError(f"{what}: 1 <= pr_num <= {VIDEOVAL_MAX_THRESHOLDS}, got {pr}")
+    if stats.dtype != torch.int64 or not stats.is_contiguous() or stats.numel() < 4 * n:
+        raise _lib.CavpError(f"{what}: stats must be a dense int64 tensor of at least [{n}, 4]")
+    if hist.dtype != torch.int32 or not hist.is_contiguous() or hist.numel() < n * 2 * (pr + 1):
+        raise _lib.CavpError(f"{what}: hist must be a dense int32 tensor of at least [{n}, 2, {pr + 1}]")
+    if state.dtype != torch.int64 or not state.is_contiguous() or state.numel() != VIDEOVAL_STATE_WORDS:
+        raise _lib.CavpError(f"{what}: state must be a dense int64 [{VIDEOVAL_STATE_WORDS}] tensor")
+
+
+def _videoval_count(count: Optional[torch.Tensor], n: int, T: int, what: str) -> Tuple[int, int]:
+    """(B, count_i64) of N = B * T frames and the optional count [B]."""
+    T = int(T)
+    if T < 1 or n < 1 or n % T:
+        raise _lib.CavpError(f"{what}: {n} frames are no whole number of videos of T = {T}")
+    B = n // T
+    if n > 65535:
+        raise _lib.CavpError(f"{what}: at most 65535 frames in one call, got {n}")
+    if count is not None:
+        if not isinstance(count, torch.Tensor) or count.dtype not in (torch.int32, torch.int64) or tuple(count.shape) != (B,) \
+                or not count.is_contiguous():
+            raise _lib.CavpError(f"{what}: count must be a dense int32 or int64 tensor of shape ({B},)")
+    return B, 1 if count is not None and count.dtype == torch.int64 else 0
+
+
+def videoval_frame_stats(pred: torch.Tensor, labels: torch.Tensor, count: Optional[torch.Tensor], T: int, num_classes: int, ignore: int,
+                         thresholds: torch.Tensor, stats: torch.Tensor, hist: torch.Tensor, M: torch.Tensor, state: torch.Tensor,
+                         channel: int = 1, prob: Optional[torch.Tensor] = None) -> None:
+    """One pass over the prediction of N = B * T frames (include/cavp_hip.h, cavp_videoval_frame_stats): per frame n that takes part
+    (t < clamp(count[b], 0, T); count None: all) stats[n, 4] (int64) += the sums of mask_iou_stats, hist[n, 2, pr_num + 1] (int32) +=
+    the histograms of fmeasure_hist, and M[(K+1) * K] (int64) += the counts of seg_confusion.  pred: dense f32 logits [N, C, H, W]
+    with 2 <= C <= K, or a dense uint8 class mask [N, H, W] together with prob, a dense f32 [N, H, W] plane (seg_predict's
+    outputs).  labels: dense int64 with N * H * W elements ending in [H, W]; thresholds: ascending f32 [pr_num]; state: int64 [8]."""
+    E = _lib.CavpError
+    if not isinstance(pred, torch.Tensor) or not isinstance(labels, torch.Tensor):
+        raise E("videoval_frame_stats: pred and labels are tensors")
+    is_mask = pred.dtype == torch.uint8
+    k = int(num_classes)
+    if is_mask:
+        if pred.dim() != 3 or not pred.is_contiguous():
+            raise E(f"videoval_frame_stats: a dense uint8 class mask [N, H, W] required, got {tuple(pred.shape)}")
+        if prob is None or prob.dtype != torch.float32 or tuple(prob.shape) != tuple(pred.shape) or not prob.is_contiguous():
+            raise E(f"videoval_frame_stats: a mask comes with a dense float32 probability plane of its shape {tuple(pred.shape)}")
+        c = 0
+    elif pred.dtype == torch.float32:
+        if pred.dim() != 4 or not pred.is_contiguous():
+            raise E(f"videoval_frame_stats: dense float32 logits [N, C, H, W] required, got {tuple(pred.shape)}")
+        c = pred.shape[1]
+        if c < 2 or not 0 <= int(channel) < c:
+            raise E(f"videoval_frame_stats: logits need C >= 2 and 0 <= channel < C (C={c}, channel={channel})")
+        if k < c:
+            raise E(f"videoval_frame_stats: num_classes {k} < logit channels {c}")
+        if prob is not None:
+            raise E("videoval_frame_stats: prob comes with a uint8 mask only")
+    else:
+        raise E(f"videoval_frame_stats: pred is a uint8 class mask [N, H, W] or float32 logits [N, C, H, W], got {pred.dtype}")
+    n, h, w = pred.shape[0], pred.shape[-2], pred.shape[-1]
+    if n < 1 or h < 1 or w < 1:
+        raise E("videoval_frame_stats: empty inputs are not supported")
+    if labels.dtype != torch.int64 or labels.dim() < 3 or labels.numel() != n * h * w or tuple(labels.shape[-2:]) != (h, w) \
+            or not labels.is_contiguous():
+        raise E(f"videoval_frame_stats: dense int64 labels of {n} frames of {(h, w)} required, got {labels.dtype} {tuple(labels.shape)}")
+    B, i64 = _videoval_count(count, n, T, "videoval_frame_stats")
+    pr = thresholds.numel()
+    if thresholds.dtype != torch.float32 or not thresholds.is_contiguous():
+        raise E("videoval_frame_stats: dense float32 thresholds required")
+    _videoval_scratch(stats, hist, state, n, pr, "videoval_frame_stats")
+    _check_counts(M, k, "videoval_frame_stats")
+    _need_gpu(pred, prob, labels, count, thresholds, stats, hist, M, state)
+    st = _lib.load().cavp_videoval_frame_stats(_ptr(pred), 1 if is_mask else 0, _ptr(prob), _ptr(labels), _ptr(count), i64, B, int(T), c,
+                                               int(channel), h * w, k, int(ignore), _ptr(thresholds), pr, _ptr(stats), _ptr(hist),
+                                               _ptr(M), _ptr(state), C.c_void_p(_stream()))
+    _lib.check(st, f"cavp_videoval_frame_stats B{B} T{T} C{c} HW{h * w} K{k}")
+
+
+def videoval_combine(stats: torch.Tensor, hist: torch.Tensor, count: Optional[torch.Tensor], B: int, T: int, hw: int, pr_num: int,
+                     J: torch.Tensor, F: torch.Tensor, state: torch.Tensor) -> None:
+    """The float32 tail of videoval_frame_stats' scratch (include/cavp_hip.h, cavp_videoval_combine): J and F (dense f32 [max_videos])
+    of every video with frames into the next free slots, state[4] advanced on the device, the scratch written back to zero."""
+    E = _lib.CavpError
+    B, T, hw, pr = int(B), int(T), int(hw), int(pr_num)
+    if B < 1 or hw < 1:
+        raise E("videoval_combine: B >= 1 and HW >= 1")
+    _videoval_count(count, B * T, T, "videoval_combine")
+    _videoval_scratch(stats, hist, state, B * T, pr, "videoval_combine")
+    if J.dtype != torch.float32 or F.dtype != torch.float32 or not (J.is_contiguous() and F.is_contiguous()) or J.dim() != 1 \
+            or J.shape != F.shape or J.numel() < 1:
+        raise E("videoval_combine: J and F must be dense float32 [max_videos] tensors of one size")
+    _need_gpu(stats, hist, count, J, F, state)
+    i64 = 1 if count is not None and count.dtype == torch.int64 else 0
+    st = _lib.load().cavp_videoval_combine(_ptr(stats), _ptr(hist), _ptr(count), i64, B, T, hw, pr, J.numel(), _ptr(J), _ptr(F),
+                                           _ptr(state), C.c_void_p(_stream()))
+    _lib.check(st, f"cavp_videoval_combine B{B} T{T} HW{hw}")

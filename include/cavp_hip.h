@@ -807,6 +807,54 @@ int cavp_clipval_combine(uint32_t* hist, uint32_t* conf, uint32_t* flags, const 
                          int32_t K, int32_t min_count, int32_t min_values, uint64_t* counts, int64_t* frames, int64_t* state,
                          void* stream);
 
+/* ---- Video validation (two entry points added to ABI 16; nothing else changed): the per-video J (mask IoU) and F (best F-measure)
+ * of the AVSBench object trainer's validation loop (trainer_cavp_avs_obj.py:292-363) for a batch of B videos of T frames at once,
+ * restated in tests/_videoval_ref.py ----
+ * Frame n = b * T + t takes part iff t < clamp(count[b], 0, T) (count as for clip validation above; NULL: all frames).  A frame
+ * that does not take part is not read.  Every pixel of a participating frame has a label v (labels: dense int64 [B*T][HW], never
+ * written), a predicted class p and a probability q:
+ *   pred_is_mask == 0: pred is dense f32 logits [B*T][C][HW], 2 <= C <= K (any 4-byte aligned base; prob is ignored); p = argmax
+ *     over C (first maximal index, a NaN counts as the maximum), q = expf(x[channel] - m) / sum_c expf(x[c] - m), m = max_c x[c]:
+ *     the expression, and so the bits, of the F-measure histogram entry point above with C >= 2;
+ *   pred_is_mask != 0: pred is a dense u8 class mask [B*T][HW] and prob a dense f32 plane [B*T][HW] (the two outputs of
+ *     cavp_seg_predict_nhwc); p = the mask byte, q = the plane's value (C and channel are ignored).
+ * 16-byte loads when HW % 4 == 0 and the bases are 16-byte aligned (mask: 4 bytes), element loads otherwise.  With C <= 4 the
+ * logits of a pixel are loaded once and held in registers; wider logits are loaded a second time for the softmax.
+ *
+ * cavp_videoval_frame_stats, per participating frame, all integer adds:
+ *   stats[n][4] (int64 scratch) += sum p*v, sum max(p, v), sum (1-v)(1-p), sum v: cavp_mask_iou_stats of (p as int64, labels);
+ *   hist[n][2][pr_num+1] (u32 scratch) += the histogram of bin(q) = #{i : thresholds[i] <= q} over all pixels ([n][0]) and over
+ *     v != 0 ([n][1]): cavp_fmeasure_hist;
+ *   M[(K+1)*K] (u64, global) += the confusion counts of cavp_seg_confusion_nchw (v < 0 or v == ignore: no count; row = v < K ? v : K),
+ *     privatised per workgroup in LDS when thresholds, histograms and counts fit 64 KiB together.
+ *   state[0] += the labels outside {0, 1, ignore} (they are still counted by the rules above); state[1] += the mask bytes >= K
+ *   (counted in stats and hist, no confusion bin): no label or mask value indexes memory unguarded.
+ *   thresholds: ascending f32 [pr_num], 1 <= pr_num <= CAVP_VIDEOVAL_MAX_THRESHOLDS.  K <= CAVP_METRICS_MAX_CLASSES.
+ * cavp_videoval_combine, one workgroup per video b with c = clamp(count[b], 0, T) > 0 frames, float32, IEEE operations, no
+ *   contraction:
+ *   J = (sum over t < c ascending of o_t / (u_t + 1e-7)) / c with (o_t, u_t) = (stats[n][0], stats[n][1]), or (stats[n][2], HW)
+ *     when stats[n][3] == 0 (mask_iou's empty-target substitution);
+ *   per frame and threshold i: tp = sum_{k > i} hist[n][1][k], prec = tp / (sum_{k > i} hist[n][0][k] + 1e-20), recall = tp /
+ *     (ysum + 1e-20) with ysum = sum_k hist[n][1][k], f = 1.3 prec recall / (0.3 prec + recall), NaN -> 0; the f of the frames with
+ *     ysum > 0 are added in ascending t and divided by the number of those frames (none: 0); F = the maximum over i.
+ *   J[slot] and F[slot] (f32 [max_videos]) with slot = state[4] + #{b' < b : clamp(count[b']) > 0}: batch order within a call, call
+ *   order across calls; a video with c == 0 takes no slot, one with slot >= max_videos is not stored and counted in state[3].  The
+ *   last workgroup to finish (a ticket in state[5], left at 0) adds the number of videos of this call to state[4]: no host read,
+ *   the same on every graph replay.  state[2] += the count[b] outside [0, T].  Writes stats and hist of the participating frames
+ *   back to zero.
+ * stats and hist must hold at least B*T frames and be ZERO before the first call; combine leaves them zero, so nothing is cleared
+ * outside the launches.  state: int64 [8] (device, persistent) {labels outside {0, 1, ignore}, mask bytes >= K, bad counts, videos
+ * dropped, videos seen, ticket, reserved, reserved}.  Launch order on one stream: frame_stats, combine, with the same count, B, T,
+ * HW and pr_num.  B*T <= 65535, HW < 2^31.  The integer results are independent of arrival order, the float tail runs in a fixed
+ * order.  No allocation, no synchronisation, no host read of a device value: capturable in a hipGraph. */
+#define CAVP_VIDEOVAL_MAX_THRESHOLDS 1024
+int cavp_videoval_frame_stats(const void* pred, int32_t pred_is_mask, const float* prob, const int64_t* labels, const void* count,
+                              int32_t count_i64, int32_t B, int32_t T, int32_t C, int32_t channel, int64_t HW, int32_t K,
+                              int64_t ignore, const float* thresholds, int32_t pr_num, int64_t* stats, uint32_t* hist, uint64_t* M,
+                              int64_t* state, void* stream);
+int cavp_videoval_combine(int64_t* stats, uint32_t* hist, const void* count, int32_t count_i64, int32_t B, int32_t T, int64_t HW,
+                          int32_t pr_num, int32_t max_videos, float* J, float* F, int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
