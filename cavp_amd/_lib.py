@@ -188,6 +188,10 @@ PROTOTYPES = {
     "cavp_videoval_frame_stats": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp,
                                          _vp, _vp]),
     "cavp_videoval_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # ---- wave stage: resample, crop and mix raw audio clips (added to ABI 16) ----
+    "cavp_wave_tile": (_i32, []),
+    "cavp_wave_stage": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32,
+                               _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

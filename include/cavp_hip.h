@@ -855,6 +855,35 @@ int cavp_videoval_frame_stats(const void* pred, int32_t pred_is_mask, const floa
 int cavp_videoval_combine(int64_t* stats, uint32_t* hist, const void* count, int32_t count_i64, int32_t B, int32_t T, int64_t HW,
                           int32_t pr_num, int32_t max_videos, float* J, float* F, int64_t* state, void* stream);
 
+/* ---- Wave stage (two entry points added to ABI 16; nothing else changed): the mono 16 kHz window the reference's data sets cut
+ * on the host from a decoded file - Resample(rate, 16000), crop_audio, the sum over the sources resp. the mean over the channels,
+ * the one second of a clip (vpo_mono/multi_source/audio/audio_dataset.py:48-70, avss/audio/audio_dataset.py:42-62,
+ * avsbench_ms.py:129-134,156-159,169-180, avsbench_s4.py:120-149) - as ONE launch, restated in tests/_wave_ref.py ----
+ * raw: [B][S][C][Lmax] float32 (raw_i16 == 0) or int16 (raw_i16 != 0; v stands for v / 32768), contiguous, never written.
+ * length, rate_idx, n_ch: int32 [B][S]; select: int32 [B] or NULL.  Per row b, source s with L = length[b][s] > 0, channel c < n_ch:
+ *   resample: rate_desc[r] = {o, n, span, stride, tap_off, first_off, shift, fspread} (int32 [n_rates][8], device) with o : n the
+ *     reduced ratio rate : 16000; taps + tap_off is the compact float32 filter [n][stride] (the live taps of phase p first, zeros up
+ *     to `span`; stride >= span), first + first_off the int32 [n] index of the first live tap of each phase less its minimum,
+ *     shift = that minimum less the filter's half width, fspread = the largest entry of first.  L16 = ceil(n * L / o) (64-bit);
+ *     y[j] = sum over k < span, ascending, fmaf, of taps[p][k] * xz[(j / n) * o + shift + first[p] + k], p = j % n, xz zero outside
+ *     [0, L).  Rate 16000 is {1, 1, 1, 1, ..} with the single tap 1.0f: y = x bit for bit.
+ *   crop: mid = L16 / 2, st = mid - sample_len / 2, s0 = st >= 0 ? st : max(L16 + st, 0), s1 = min(st + sample_len, L16),
+ *     ln = s1 - s0; w[i] = y[s0 + (ln == sample_len ? i : i % ln)]: crop_audio's slice with its negative-start wrap and repeat.
+ *   reduce: m_s[i] = (sum over c ascending of w_{s,c}[i]) / n_ch; out[i] = sum over the present sources ascending of m_s[i].
+ *   select != NULL: out holds A_out = sample_len / segments values per row, i = select[b] * A_out + a; else A_out = sample_len.
+ * Only the window of y is computed.  out: float32 [B][A_out].
+ * Bad input - a length outside [0, Lmax], a rate_idx outside [0, n_rates) or an n_ch outside [1, C] of a present source, a select
+ * outside [0, segments), a rate_desc entry that does not fit the three LDS capacities - adds 1 per value to state[0] (int64 [4],
+ * device, persistent) and the row is written as zeros; no input value makes the kernel read or write out of bounds.
+ * LDS: tab_cap floats for one rate's filter, first_cap int32 for its first-tap indices, x_cap floats for the input span of one
+ * tile of cavp_wave_tile() outputs: x_cap >= ((tile - 1) / n + 1) * o + fspread + span for every rate; together at most 160 KiB.
+ * Lmax <= 2^28.  No allocation, no synchronisation, no host read of a device value: capturable in a hipGraph. */
+int cavp_wave_tile(void);
+int cavp_wave_stage(const void* raw, int32_t raw_i16, const int32_t* length, const int32_t* rate_idx, const int32_t* n_ch,
+                    const int32_t* select, int32_t B, int32_t S, int32_t C, int64_t Lmax, int32_t sample_len, int32_t segments,
+                    const int32_t* rate_desc, int32_t n_rates, const float* taps, const int32_t* first, int32_t tab_cap,
+                    int32_t first_cap, int32_t x_cap, int64_t* state, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
-                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize]]]
+                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]]]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -29,7 +29,8 @@ overwrite for step 0, one with it for the rest.  The loop is "copy the batch int
 class indices - and the captured prologue is the whole input chain FrameAugment -> LabelStage -> PairBuilder -> MelFrontEnd: the
 image labels the pair builder sees are computed on the device from the augmented, remapped mask, as the reference's data sets
 compute them after their transform.  --resize: the AVSS set-ups' variant (the AVS scale list, no jitter, a resize to --hw instead
-of pad + crop).
+of pad + crop).  --raw-audio: the clips are raw material too - 10 s of synthetic 44.1 kHz int16 stereo PCM per row - and
+cavp_amd.wave.WaveStage (resample to 16 kHz, centre crop to one second, channel mean) stands at the head of the prologue.
 """
 import argparse
 import os
@@ -67,7 +68,10 @@ def main():
     ap.add_argument("--graph", action="store_true", help="one hipGraph per iteration: pairs, log-mel, step and optimiser (device schedule)")
     ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
     ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
+    ap.add_argument("--raw-audio", action="store_true", help="with --augment: 44.1 kHz int16 stereo PCM through WaveStage at the head of the prologue")
     a = ap.parse_args()
+    if a.raw_audio and not a.augment:
+        ap.error("--raw-audio needs --augment")
     if a.augment and not a.graph:
         ap.error("--augment needs --graph (with --from-waveform --contrast --pairs)")
     if a.resize and not a.augment:
@@ -142,8 +146,16 @@ def main():
                 masks[b, y:y + stage[0] // 3, x:x + stage[1] // 3] = RAW0 + c
         return frames, masks
 
+    RAW_RATE, RAW_LEN = 44100, 441000      # --raw-audio: 10 s of stereo PCM per row
+
+    def draw_raw_audio():
+        """B clips of int16 stereo PCM (host) and their lengths, 5 .. 10 s"""
+        pcm = torch.randint(-3277, 3278, (B, 1, 2, RAW_LEN), dtype=torch.int16, generator=g)
+        return pcm, torch.randint(RAW_LEN // 2, RAW_LEN + 1, (B, 1), dtype=torch.int32, generator=g)
+
     replays = None
     aug = None
+    wave_stage = None
     if a.graph:
         from cavp_amd.pairs import PairResult
         s_image = torch.zeros(B, 3, a.hw, a.hw, device=dev)
@@ -171,6 +183,15 @@ def main():
             s_masks = torch.zeros((B,) + stage, dtype=torch.uint8, device=dev)
             s_sizes = torch.tensor([list(stage)] * B, dtype=torch.int32, device=dev)
             augmented, labelled = AugResult(B, (a.hw, a.hw), dev), LabelResult(B, pairs.K, (a.hw, a.hw), dev, True)
+        if a.raw_audio:
+            from cavp_amd.wave import WaveResult, WaveStage
+            wave_stage = WaveStage(audio_len=hyp.audio_len, rates=(RAW_RATE,), max_sources=1, max_channels=2, max_len=RAW_LEN,
+                                   device=dev, max_batch=B)
+            s_pcm = torch.zeros((B, 1, 2, RAW_LEN), dtype=torch.int16, device=dev)
+            s_pcm_len = torch.full((B, 1), RAW_LEN, dtype=torch.int32, device=dev)
+            s_rate_idx = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+            s_n_ch = torch.full((B, 1), 2, dtype=torch.int32, device=dev)
+            cut = WaveResult(B, 16000, dev)
 
         def prologue_of(overwrite):
             def prologue():
@@ -180,7 +201,9 @@ def main():
                     s_image.copy_(augmented.image)
                     s_label.copy_(labelled.label)
                     s_img_label.copy_(labelled.img_label)
-                pairs(s_wave, s_label, s_img_label, overwrite, out=built)
+                if wave_stage is not None:   # raw PCM -> the mono 16 kHz second the pair builder takes
+                    wave_stage(s_pcm, s_pcm_len, s_rate_idx, s_n_ch, out=cut)
+                pairs(s_wave if wave_stage is None else cut.waveform, s_label, s_img_label, overwrite, out=built)
                 s_audio.copy_(front(built.waveforms))
                 s_shuf.copy_(built.label_shuffle)
             return prologue
@@ -208,6 +231,9 @@ def main():
                 frames, masks = draw_raw_batch(tuple(s_masks.shape[1:]))
                 for dst, src in ((s_frames, frames), (s_masks, masks), (s_wave, wave)):
                     dst.copy_(src)
+                if wave_stage is not None:
+                    for dst, src in zip((s_pcm, s_pcm_len), draw_raw_audio()):
+                        dst.copy_(src)
             else:
                 for dst, src in ((s_image, image), (s_label, label), (s_wave, wave), (s_img_label, img_label)):
                     dst.copy_(src)
@@ -269,6 +295,10 @@ def main():
         stage_labels.check()
         print(f"input chain: {'resize' if a.resize else 'pad + crop'} augmentation, img_label from the augmented mask: "
               f"{labelled.img_label[:, 1:].sum(0).tolist()} frames per foreground class in the last batch")
+    if rank == 0 and wave_stage is not None:
+        wave_stage.check()
+        print(f"raw audio: {RAW_LEN / RAW_RATE:.0f} s of {RAW_RATE} Hz int16 stereo per row -> [B, 1, 16000] by WaveStage; rms of the last batch "
+              f"{float(cut.waveform.square().mean().sqrt()):.4f}")
     if rank == 0 and a.fixed_batch:
         print(f"fixed batch: loss {first:.4f} -> {float(loss.item()):.4f} after {a.steps} steps")
     if world > 1:
