@@ -94,6 +94,13 @@ PROTOTYPES = {
     "cavp_optimizer_state_bytes": (C.c_int64, []),
     "cavp_optimizer_schedule": (_i32, [_vp, _vp]),
     "cavp_optimizer_step_dev": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp]),
+    # step guard: gradient norm, clipping, non-finite skip and the record ring on the GPU (added to ABI 16)
+    "cavp_guard_state_bytes": (C.c_int64, []),
+    "cavp_step_record_bytes": (C.c_int64, []),
+    "cavp_grad_guard_partials": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "cavp_grad_guard_finish": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "cavp_optimizer_schedule_guarded": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "cavp_optimizer_step_guarded": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp]),
     "cavp_mel_frontend": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp]),
     "cavp_unpack_weight_grad": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_conv3x3_smallcin_wgrad": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),

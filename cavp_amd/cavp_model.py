@@ -954,7 +954,8 @@ class CAVP(nn.Module):
         backward + update at the next step of the schedule.  With collectives on the all-reduce runs between the graphs and
         the host, so the update cannot be in a graph: replay() issues optimizer.step() behind the late all-reduce instead
         (no synchronisation either).  `p.grad` stay valid after a replay, and one optimiser may be recorded in several graphs
-        (they share its device state).
+        (they share its device state).  If the optimiser has a StepGuard (FusedSGDAdam.use_step_guard) its four launches take the
+        update's place, in the same position, and each replay's record carries that replay's losses.
         prologue: a callable run first in each of the three passes (two warm-ups, the capture) on that pass's stream; it writes
         the static `audio` / `label_shuffle` buffers, which puts the input pipeline into the same graph:
             def prologue():
@@ -970,6 +971,11 @@ class CAVP(nn.Module):
             if getattr(self, "_grad_arena", None) is None or optimizer._arena is not self._grad_arena \
                     or self._grad_arena.flat.device != image.device:
                 raise CavpError("capture_train_step: the optimiser was not built on this model's gradient arena")
+            guard = getattr(optimizer, "_guard", None)
+            if guard is not None and guard.skip_nonfinite_loss and collectives_on():
+                raise CavpError("capture_train_step: the guard's loss rule would decide on this rank's own loss while the gradients "
+                                "are reduced over all ranks, and the replicas would part; build it with "
+                                "StepGuard(skip_nonfinite_loss=False) for data-parallel runs (the losses are still recorded)")
         if prologue is not None and not callable(prologue):
             raise CavpError("capture_train_step: prologue must be callable")
         opt_in_graph = optimizer is not None and not collectives_on()
@@ -981,6 +987,18 @@ class CAVP(nn.Module):
         world = dist_world()
         if split is None:
             split = collectives_on()
+
+        static_losses = []
+
+        def step_update(loss):
+            # a StepGuard's record carries the step's losses: (l_ce, l_ctr) with the contrast term, else the loss itself; the
+            # captured pass's tensors are the ones every replay writes, so they are taken once
+            if getattr(optimizer, "_guard", None) is None:
+                optimizer.step()
+                return
+            if not static_losses:
+                static_losses.append(tuple(self._last_losses) if contrast is not None else (loss,))
+            optimizer.step(losses=static_losses[0])
         with torch.no_grad():
             pro()
             self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)   # warm-up: workspace, arena
@@ -998,7 +1016,7 @@ class CAVP(nn.Module):
                     pro()
                     loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False, **ctr)
                     if opt_in_graph:
-                        optimizer.step()   # last on the capture stream: every branch has been joined by now
+                        step_update(loss)   # last on the capture stream: every branch has been joined by now
                 graphs = (graph,)
             else:
                 g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -1016,11 +1034,13 @@ class CAVP(nn.Module):
                     loss = self.train_step(image, audio, label, ignore_index, loss_scale / world, all_reduce=False,
                                            _split_hook=cut, **ctr)
                     if opt_in_graph:
-                        optimizer.step()
+                        step_update(loss)
                     g2.capture_end()
                 torch.cuda.current_stream().wait_stream(cap)
                 graphs = (g1, g2)
         arena = self._grad_arena
+        if optimizer is not None and not static_losses:   # collectives on: the update was not issued during the capture
+            static_losses.append(tuple(self._last_losses) if contrast is not None else (loss,))
 
         def replay():
             self.params_changed()   # the graph updates the running statistics (and is usually followed by an optimiser step)
@@ -1035,7 +1055,7 @@ class CAVP(nn.Module):
             elif collectives_on():
                 allreduce_arena_late(arena, None)
             if optimizer is not None and not opt_in_graph:
-                optimizer.step()   # the all-reduce is outside the graphs, so the update is too: eager, behind it on the stream
+                step_update(loss)   # the all-reduce is outside the graphs, so the update is too: eager, behind it on the stream
             return loss
         # keep alive: the graphs, and every scratch buffer whose address they baked in (ops.workspace never frees a buffer it
         # has handed out, see there)

@@ -468,6 +468,70 @@ int cavp_optimizer_schedule(cavp_opt_state* state_device, void* stream);
 int cavp_optimizer_step_dev(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum, float eps,
                             const cavp_opt_state* state_device, void* stream);
 
+/* Step guard (added to ABI 16): global gradient norm, clip_grad_norm_ clipping, a skip of the whole update when a gradient is
+ * not finite, and a ring of per-step records, all on the device so that a captured iteration needs no host value for them.
+ * One guarded step is four launches on one stream, each ordered behind the one before it by the stream alone:
+ *   cavp_grad_guard_partials -> cavp_grad_guard_finish -> cavp_optimizer_schedule_guarded -> cavp_optimizer_step_guarded.
+ * The host fills max_norm, skip_nonfinite and history (and zeroes the rest) once; the device writes everything else.
+ * The ring of `history` cavp_step_record follows the state block directly, at byte offset cavp_guard_state_bytes(). */
+typedef struct cavp_guard_state {
+  float max_norm;          /* <= 0: no clipping */
+  int32_t skip_nonfinite;  /* CAVP_GUARD_SKIP_* bits; 0: never skip */
+  int32_t history;         /* capacity of the record ring, >= 1 */
+  int32_t skip;            /* from here on: written by the device, every step */
+  float grad_norm;         /* 2-norm over every gradient the update reads */
+  float norm_sgd;          /* ... over the kind 0 jobs */
+  float norm_adam;         /* ... over the kind 1 jobs */
+  float clip_coef;         /* max_norm > 0 ? min(1, max_norm / (grad_norm + 1e-6)) : 1 (torch's clip_grad_norm_) */
+  int64_t nonfinite;       /* gradient elements that are NaN or +-inf */
+  int64_t skipped_total;
+  int64_t head;            /* records written so far; record i lives in slot i % history */
+} cavp_guard_state;
+#define CAVP_GUARD_SKIP_GRADIENTS 1   /* skip the update when a gradient element or the norm is not finite (the finish launch) */
+#define CAVP_GUARD_SKIP_LOSSES 2      /* ... and when a loss handed to the schedule launch is not finite; the losses are the caller's
+                                         and, data parallel, must be equal on every rank (the gradients are: the arena is reduced) */
+#define CAVP_STEP_SKIPPED 1      /* cavp_step_record.flags */
+#define CAVP_STEP_CLIPPED 2      /* clip_coef < 1 */
+#define CAVP_STEP_NO_LOSS 4      /* no loss pointer was given: l_ce is 0 */
+#define CAVP_STEP_NO_LOSS1 8     /* no second loss pointer was given: l_ctr is 0 */
+#define CAVP_STEP_SKIPPED_LOSS 16 /* skipped (also) because a loss was not finite */
+typedef struct cavp_step_record {
+  int64_t t;               /* the step index this update ran as; on a skip, the one that did not run */
+  int64_t nonfinite;
+  float l_ce;
+  float l_ctr;
+  float lr_sgd;            /* the SGD rate of step t */
+  float grad_norm;
+  float clip_coef;
+  int32_t flags;
+} cavp_step_record;
+typedef struct cavp_guard_partial {
+  float sumsq;
+  int32_t nonfinite;
+} cavp_guard_partial;
+int64_t cavp_guard_state_bytes(void);
+int64_t cavp_step_record_bytes(void);
+/* One workgroup per optimiser block (4096 elements, the update's own block -> job mapping): partials[block] = the f32 sum of
+ * squares (a 12-level tree, no chain) and the non-finite count of that block's gradients.  No atomics, every block writes its slot,
+ * the arena is read once.  partials: total_blocks entries. */
+int cavp_grad_guard_partials(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, cavp_guard_partial* partials,
+                             void* stream);
+/* One workgroup: per job the partials in a fixed lane order, then the jobs in a fixed order, all in double; then grad_norm,
+ * norm_sgd, norm_adam, nonfinite, clip_coef (from the norm in double, rounded once) and
+ * skip = (skip_nonfinite & CAVP_GUARD_SKIP_GRADIENTS) && (nonfinite > 0 || !isfinite(grad_norm)). */
+int cavp_grad_guard_finish(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks,
+                           const cavp_guard_partial* partials, cavp_guard_state* guard_device, void* stream);
+/* One thread.  guard->skip: the state block is left as it is (t, rates, bias corrections, first_step) and skipped_total grows by one;
+ * otherwise cavp_optimizer_schedule's arithmetic (one shared device function).  With CAVP_GUARD_SKIP_LOSSES a given loss that is NaN or
+ * +-inf sets guard->skip here as well, and CAVP_STEP_SKIPPED_LOSS in the record (the CE head answers "every label ignored" with a NaN loss and zero gradients).  Either way the record of this step is written to
+ * slot head % history and head grows by one.  loss0 / loss1: optional 1-element f32 device arrays (NULL: 0 and the flag). */
+int cavp_optimizer_schedule_guarded(cavp_opt_state* state_device, cavp_guard_state* guard_device, const float* loss0,
+                                    const float* loss1, void* stream);
+/* cavp_optimizer_step_dev with the gradient taken as clip_coef * g; every workgroup returns at once when guard->skip.  The
+ * gradient arena is NOT rescaled (torch.nn.utils.clip_grad_norm_ scales p.grad in place; here p.grad keeps the raw gradient). */
+int cavp_optimizer_step_guarded(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum, float eps,
+                                const cavp_opt_state* state_device, const cavp_guard_state* guard_device, void* stream);
+
 /* ---- log-mel front-end = trainers' preprocess_audio (trainer_cavp_vpo_mono.py:43-52,59-69;
  * utils/sourcesep.py:23-47): STFT(n_fft 512, hop, centred window, reflect padding) -> |.|^2 -> mel filterbank ->
  * 20 log10(max(amin, x)) -> 2 (x - spec_min) / (spec_max - spec_min) - 1.

@@ -11,7 +11,8 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
-                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]]]
+                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]]
+                                   [--guard [--max-norm X]]]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -31,6 +32,10 @@ image labels the pair builder sees are computed on the device from the augmented
 compute them after their transform.  --resize: the AVSS set-ups' variant (the AVS scale list, no jitter, a resize to --hw instead
 of pad + crop).  --raw-audio: the clips are raw material too - 10 s of synthetic 44.1 kHz int16 stereo PCM per row - and
 cavp_amd.wave.WaveStage (resample to 16 kHz, centre crop to one second, channel mean) stands at the head of the prologue.
+
+--guard (with --graph): a cavp_amd.optim.StepGuard on the recorded update - global gradient norm, --max-norm clipping, the whole
+update skipped when a gradient or a loss is not finite.  The loop then reads no loss back per step: every 5 steps one guard.read()
+returns the records written since (step, rate, both losses, gradient norm, coefficient, skipped / clipped) and they are printed.
 """
 import argparse
 import os
@@ -66,6 +71,9 @@ def main():
     ap.add_argument("--pairs", action="store_true", help="build the shuffled half of the batch and its labels with PairBuilder")
     ap.add_argument("--ow-rate", type=float, default=0.5, help="share of the mismatched rows overwritten from the sound bank")
     ap.add_argument("--graph", action="store_true", help="one hipGraph per iteration: pairs, log-mel, step and optimiser (device schedule)")
+    ap.add_argument("--guard", action="store_true", help="with --graph: StepGuard on the recorded update (gradient norm, non-finite skip); "
+                    "the progress lines come from guard.read(), one synchronisation per 5 steps instead of .item() reads")
+    ap.add_argument("--max-norm", type=float, default=None, help="with --guard: clip the global gradient norm to this bound")
     ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
     ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
     ap.add_argument("--raw-audio", action="store_true", help="with --augment: 44.1 kHz int16 stereo PCM through WaveStage at the head of the prologue")
@@ -78,6 +86,10 @@ def main():
         ap.error("--resize needs --augment")
     if a.pairs and not (a.from_waveform and a.contrast):
         ap.error("--pairs needs --from-waveform and --contrast")
+    if a.guard and not a.graph:
+        ap.error("--guard needs --graph: the guard lives beside the device schedule of the recorded update")
+    if a.max_norm is not None and not a.guard:
+        ap.error("--max-norm needs --guard")
     if a.graph and not a.pairs:
         ap.error("--graph needs --from-waveform --contrast --pairs")
 
@@ -168,6 +180,11 @@ def main():
         built = PairResult(B, 16000, pairs.K, (a.hw, a.hw), dev)
         opt = FusedSGDAdam(model, model.grad_arena(dev), a.lr, momentum=a.momentum, weight_decay=a.weight_decay)
         opt.use_device_schedule(a.lr, a.lr_power, a.total_iters, 0)
+        guard = None
+        if a.guard:
+            from cavp_amd.optim import StepGuard
+            guard = StepGuard(max_norm=a.max_norm, skip_nonfinite=True, history=64)
+            opt.use_step_guard(guard)                           # before the captures: they record its four launches
         start = {k: v.clone() for k, v in model.state_dict().items()}
 
         if a.augment:
@@ -242,6 +259,18 @@ def main():
             if it == 1:
                 torch.cuda.synchronize()
                 t0 = time.time()
+            if guard is not None:                               # the display_iter pattern: one read per 5 steps, every step shown
+                if it % 5 == 4 or it == a.steps - 1:
+                    rec = guard.read()
+                    if first is None and len(rec["t"]):
+                        first = float(rec["l_ce"][0] + a.contrast_weight * rec["l_ctr"][0])
+                    for i in range(len(rec["t"]) if rank == 0 else 0):
+                        mark = " SKIPPED" if rec["skipped"][i] else (" clipped" if rec["clipped"][i] else "")
+                        print(f"step {int(rec['t'][i]):4d}  lr {rec['lr'][i]:.3e}  CE {rec['l_ce'][i]:.4f}  contrast {rec['l_ctr'][i]:.4f}  "
+                              f"|g| {rec['grad_norm'][i]:.3e}  coef {rec['clip_coef'][i]:.3f}{mark}", flush=True)
+                    if rec["dropped"]:
+                        print(f"({rec['dropped']} records overwritten before this read)")
+                continue
             if first is None:
                 first = float(loss.item())
             if rank == 0 and (it % 5 == 0 or it == a.steps - 1):
