@@ -199,6 +199,9 @@ PROTOTYPES = {
     "cavp_wave_tile": (_i32, []),
     "cavp_wave_stage": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32,
                                _i32, _vp, _vp, _vp]),
+    # ---- preview stage: x / y / y_tilde panels as bytes, optional NEAREST resize (added to ABI 16) ----
+    "cavp_preview_panels": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "cavp_preview_resize": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

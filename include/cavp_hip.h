@@ -948,6 +948,36 @@ int cavp_wave_stage(const void* raw, int32_t raw_i16, const int32_t* length, con
                     const int32_t* rate_desc, int32_t n_rates, const float* taps, const int32_t* first, int32_t tab_cap,
                     int32_t first_cap, int32_t x_cap, int64_t* state, float* out, void* stream);
 
+/* ---- Preview stage (two entry points added to ABI 16; nothing else changed): the three pictures per frame of the reference's
+ * Tensorboard.upload_wandb_image (utils/tensor_board.py:90-139) - the de-normalised frame x, the label y and the prediction y_tilde -
+ * as bytes on the device, restated in tests/_preview_ref.py.  y and y_tilde are PALETTE INDICES, one byte per pixel; the palette
+ * (get_pallete / colorize_mask) is applied on the host ----
+ * cavp_preview_panels, B images of HW pixels, every input dense and never written:
+ *   x [HW][3] (RGB interleaved), from image f32 [B][3][HW] and mean_std f32 [6] on the device (mean of R, G, B, then std): per
+ *     channel v = t * std; v = v + mean; u = v * 255 - three separately rounded float32 operations, never contracted into a fused
+ *     multiply-add (DeNormalize's t.mul_(s).add_(m), then ToPILImage's pic.mul(255).byte()); the byte is u truncated toward zero,
+ *     taken mod 256 (-1.5 -> 255, 256.7 -> 0, 300 -> 44).  A non-finite u or |u| >= 2^31 writes 0 and adds 1 to state[0] (int64 [4],
+ *     device, persistent).  image == NULL (then x == NULL): no x panel.
+ *   y [HW], from labels int64 (label_u8 == 0) or uint8 (label_u8 != 0) [B][HW]: the value mod 256 (-1 -> 255, 259 -> 3), numpy's
+ *     astype(uint8).  labels == NULL (then y == NULL): no y panel and no propagation below.
+ *   y_tilde [HW]: the prediction p, overwritten with 255 where the RAW label equals `ignore` (compared before the wrap: a -1 label
+ *     does not propagate).  pred_is_mask == 0: pred is f32 logits [B][C][HW], 1 <= C <= 256, p = argmax over C (first maximal index,
+ *     a NaN counts as the maximum: torch.argmax, the rule of the confusion entry points); every logit is read exactly once.
+ *     pred_is_mask != 0: pred is a u8 class mask [B][HW] (what cavp_seg_predict_nhwc writes; C is ignored), p = the byte.
+ *   Image b's panels start out_stride bytes after image b-1's (out_stride >= the bytes of the present panels).
+ *   One thread handles 4 consecutive pixels: 16-byte loads per channel plane and whole-dword stores (three for x, one each for y and
+ *   y_tilde) when HW % 4 == 0, out_stride % 4 == 0 and every base is aligned (f32 and int64: 16 bytes, bytes: 4); element accesses
+ *   otherwise.  No atomics except the bad counter.
+ * cavp_preview_resize: the panels of B images in the dense per-image layout {x [H][W][3] if has_x, y [H][W] if has_y, y_tilde [H][W]}
+ *   gathered into the same layout at Ho x Wo: dst(oy, ox) = src(row_tab[oy], col_tab[ox]) (int32 [Ho] / [Wo] on the device, entries
+ *   in [0, H) / [0, W): Image.resize(NEAREST)'s source indices, made once on the host).  src and dst do not overlap.
+ * No allocation, no synchronisation, no host read of a device value: capturable in a hipGraph. */
+int cavp_preview_panels(const float* image, const float* mean_std, const void* labels, int32_t label_u8, const void* pred,
+                        int32_t pred_is_mask, int32_t B, int32_t C, int64_t HW, int64_t ignore, uint8_t* x, uint8_t* y,
+                        uint8_t* y_tilde, int64_t out_stride, int64_t* state, void* stream);
+int cavp_preview_resize(const uint8_t* src, uint8_t* dst, const int32_t* row_tab, const int32_t* col_tab, int32_t B, int32_t H,
+                        int32_t W, int32_t Ho, int32_t Wo, int32_t has_x, int32_t has_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

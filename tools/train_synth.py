@@ -12,7 +12,7 @@ shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
                                    [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]]
-                                   [--guard [--max-norm X]]]
+                                   [--guard [--max-norm X]]] [--preview DIR]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -36,6 +36,10 @@ cavp_amd.wave.WaveStage (resample to 16 kHz, centre crop to one second, channel 
 --guard (with --graph): a cavp_amd.optim.StepGuard on the recorded update - global gradient norm, --max-norm clipping, the whole
 update skipped when a gradient or a loss is not finite.  The loop then reads no loss back per step: every 5 steps one guard.read()
 returns the records written since (step, rate, both losses, gradient norm, coefficient, skipped / clipped) and they are printed.
+
+--preview DIR: after training, the reference trainers' image upload (Tensorboard.upload_wandb_image) without its whole-tensor host
+copies: eval mode, model.predict on the last batch, cavp_amd.preview.PreviewStage on image, label and mask, one 5-byte-per-pixel copy,
+and the x / y / y_tilde pictures of the first frames written to DIR as PNG files (needs PIL).
 """
 import argparse
 import os
@@ -77,6 +81,7 @@ def main():
     ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
     ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
     ap.add_argument("--raw-audio", action="store_true", help="with --augment: 44.1 kHz int16 stereo PCM through WaveStage at the head of the prologue")
+    ap.add_argument("--preview", metavar="DIR", default=None, help="after training: x / y / y_tilde PNGs of the last batch through PreviewStage")
     a = ap.parse_args()
     if a.raw_audio and not a.augment:
         ap.error("--raw-audio needs --augment")
@@ -330,6 +335,23 @@ def main():
               f"{float(cut.waveform.square().mean().sqrt()):.4f}")
     if rank == 0 and a.fixed_batch:
         print(f"fixed batch: loss {first:.4f} -> {float(loss.item()):.4f} after {a.steps} steps")
+    if rank == 0 and a.preview and a.steps > 0:
+        from cavp_amd.augment import IMAGENET_MEAN, IMAGENET_STD
+        from cavp_amd.preview import PreviewStage
+        last = (s_image, s_audio, s_label) if replays is not None else (image, audio, label)
+        model.eval()
+        mask = model.predict(last[0], last[1][:B].contiguous())            # the matched clips: the first half of the 2B
+        pv = PreviewStage(max(a.num_classes, 2), IMAGENET_MEAN, IMAGENET_STD, device=dev, max_batch=B)
+        panels = pv(last[0], last[2], mask=mask)
+        pics = pv.read(panels)
+        pv.check()
+        os.makedirs(a.preview, exist_ok=True)
+        shown = min(B, 4)
+        for name, frames in pics.items():
+            for b in range(shown):
+                frames[b].save(os.path.join(a.preview, f"{name}_{b}.png"))
+        print(f"preview: {3 * shown} PNG files in {a.preview} ({B} frames, {panels.buffer.numel()} bytes copied to the host; "
+              f"classes predicted in frame 0: {sorted(set(pics['y_tilde'][0].tobytes()))[:8]})")
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
