@@ -101,6 +101,12 @@ PROTOTYPES = {
     "cavp_grad_guard_finish": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "cavp_optimizer_schedule_guarded": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "cavp_optimizer_step_guarded": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp]),
+    # step rollback: table-driven save and guarded restore of the state a forward mutates (added to ABI 16)
+    "cavp_rollback_range_bytes": (C.c_int64, []),
+    "cavp_rollback_state_bytes": (C.c_int64, []),
+    "cavp_rollback_blocks": (C.c_int64, [C.c_int64, C.c_int64]),
+    "cavp_rollback_save": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "cavp_rollback_restore": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "cavp_mel_frontend": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp]),
     "cavp_unpack_weight_grad": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_conv3x3_smallcin_wgrad": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),

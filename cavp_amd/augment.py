@@ -170,6 +170,11 @@ class FrameAugment:
         if self._state is not None:
             self._state[:2].copy_(torch.tensor([self._seed, 0], dtype=torch.int64))
 
+    def rollback_ranges(self):
+        """[(name, tensor, byte_offset, nbytes)]: {seed, offset} of the state block, the only state a call mutates (`bad_inputs`
+        is a diagnostic and is not named).  For cavp_amd.rollback.StepRollback.add()."""
+        return [("state", self._ensure(), 0, 16)]
+
     def offset(self) -> int:
         """Synchronises: the number of calls (and replays) since the last manual_seed()."""
         return int(self._ensure()[1].item())

@@ -936,7 +936,7 @@ class CAVP(nn.Module):
 
     def capture_train_step(self, image, audio, label, ignore_index: int = 255, loss_scale: float = 1.0,
                            split: Optional[bool] = None, contrast=None, label_shuffle=None, contrast_weight: float = 1.0,
-                           optimizer=None, prologue=None):
+                           optimizer=None, prologue=None, rollback=None):
         """Capture forward_train + CE + backward (about 1000 kernel launches) into hipGraphs and return
         `replay() -> loss`.  `image`, `audio`, `label` are the static input buffers: copy new batches into them before
         each replay.  Weight packing is part of the graph, so replays always see the current parameters.
@@ -962,7 +962,14 @@ class CAVP(nn.Module):
                 built = pairs(wave, label, img_label, overwrite, out=built0)
                 audio.copy_(front(built.waveforms)); shuf.copy_(built.label_shuffle)
         The warm-up passes run it for real: a PairBuilder's and the device sampler's call counters (and the sound bank) have
-        advanced by three calls when this returns - reseed (`manual_seed`) after the capture."""
+        advanced by three calls when this returns - reseed (`manual_seed`) after the capture, unless `rollback=` is given.
+        rollback: a frozen cavp_amd.rollback.StepRollback; needs an optimiser whose StepGuard has a skip rule on.  Its save() is the
+        first launch of each pass - before the prologue, hence before any side stream forks - and its restore_if_skipped(guard)
+        follows the guarded update directly (in the graph, or behind the eager update when collectives are on): a replay whose
+        step the guard skips leaves every registered range as it found it.  The warm-up passes are undone the same way, each by
+        an unconditional restore() behind it and one more behind the capture, so the BatchNorm statistics, the bank and the call
+        counters are where they were when this returns and nothing needs reseeding; the rollback's counters are zeroed last, so
+        stats() counts replays only."""
         from .train import _no_gc_during_capture, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world
         if optimizer is not None:
             if getattr(optimizer, "_sched", None) is None:
@@ -978,8 +985,25 @@ class CAVP(nn.Module):
                                 "StepGuard(skip_nonfinite_loss=False) for data-parallel runs (the losses are still recorded)")
         if prologue is not None and not callable(prologue):
             raise CavpError("capture_train_step: prologue must be callable")
+        if rollback is not None:
+            from .rollback import StepRollback
+            guard = getattr(optimizer, "_guard", None)
+            if not isinstance(rollback, StepRollback) or not rollback._frozen:
+                raise CavpError("capture_train_step: rollback must be a frozen cavp_amd.rollback.StepRollback (freeze())")
+            if optimizer is None or guard is None:
+                raise CavpError("capture_train_step: rollback needs an optimiser with a StepGuard (FusedSGDAdam.use_step_guard): "
+                                "the guard's skip word decides the restore")
+            if not (guard.skip_nonfinite or guard.skip_nonfinite_loss):
+                raise CavpError("capture_train_step: the guard has both skip rules off, so a rollback would never restore")
+            if rollback.device != image.device:
+                raise CavpError(f"capture_train_step: the rollback lives on {rollback.device}, the inputs on {image.device}")
         opt_in_graph = optimizer is not None and not collectives_on()
-        pro = prologue if prologue is not None else (lambda: None)
+        user_pro = prologue if prologue is not None else (lambda: None)
+
+        def pro():
+            if rollback is not None:
+                rollback.save()   # the first launch of the pass: nothing has forked yet and nothing of the iteration has run
+            user_pro()
         if contrast is not None and getattr(contrast, "_dev", None) is None:
             raise CavpError("capture_train_step: the contrast term can only be captured with the device sampler "
                             "(ContrastLoss.use_device_sampler); the host sampler reads the labels and draws on the CPU every step")
@@ -999,15 +1023,23 @@ class CAVP(nn.Module):
             if not static_losses:
                 static_losses.append(tuple(self._last_losses) if contrast is not None else (loss,))
             optimizer.step(losses=static_losses[0])
+            if rollback is not None:
+                rollback.restore_if_skipped(optimizer._guard)   # directly behind the guarded update, on its stream
+
+        def undo():
+            if rollback is not None:
+                rollback.restore()   # a warm-up pass ran for real: put back what its save() took
         with torch.no_grad():
             pro()
             self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)   # warm-up: workspace, arena
+            undo()
             torch.cuda.synchronize()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 pro()
                 self.train_step(image, audio, label, ignore_index, loss_scale, all_reduce=False, **ctr)
+                undo()
             torch.cuda.current_stream().wait_stream(side)
             if not split:
                 graph = torch.cuda.CUDAGraph()
@@ -1039,6 +1071,10 @@ class CAVP(nn.Module):
                 torch.cuda.current_stream().wait_stream(cap)
                 graphs = (g1, g2)
         arena = self._grad_arena
+        if rollback is not None:
+            rollback.restore()       # the shadows hold the state from before the first warm-up pass: every pass started from it
+            rollback.reset_stats()   # stats() counts replays, not the capture's own passes
+            self.params_changed()
         if optimizer is not None and not static_losses:   # collectives on: the update was not issued during the capture
             static_losses.append(tuple(self._last_losses) if contrast is not None else (loss,))
 

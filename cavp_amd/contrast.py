@@ -342,6 +342,14 @@ class ContrastLoss(nn.Module):
         s = s - (1 << 64) if s >= (1 << 63) else s
         self._dev[1][:2].copy_(torch.tensor([s, 0], dtype=torch.int64))
 
+    def rollback_ranges(self):
+        """[(name, tensor, byte_offset, nbytes)]: {seed, offset} of the device sampler's int64[4], the state a call mutates (the
+        dropped-class and bad-label counters behind them are diagnostics and are not named).  For
+        cavp_amd.rollback.StepRollback.add()."""
+        if self._dev is None:
+            raise _lib.CavpError("rollback_ranges: call use_device_sampler() first (the host sampler keeps no device state)")
+        return [("state", self._dev[1], 0, 16)]
+
     def last_plan(self) -> dict:
         """The device tensors of the most recent device-sampler call (of the captured call, after a graph replay): `header`
         int32[4] = {n, n_match, k_eligible (classes kept), sample_num}, `idx_b`, `idx_p`, `labels` (int32[Ncap], rows >= n hold

@@ -129,9 +129,10 @@ class StepGuard:
         the caller's value, not the reduced arena's: data parallel it is rank-local, so `capture_train_step` refuses a guard with
         this switch on while collectives are on, and an eager caller must hand every rank the same (reduced) losses.
     A skipped step leaves untouched: parameters, the momentum buffer, Adam's two moment buffers, the step counter t and
-        therefore the next learning rate.  NOT rolled back: BatchNorm running statistics, the sound bank and the call counters of
-        the pair builder and the anchor sampler - the forward has already run.  A skip thus protects the weights; it does not
-        protect BatchNorm buffers from a non-finite *input*.
+        therefore the next learning rate.  NOT rolled back unless a `StepRollback` is attached (cavp_amd/rollback.py,
+        `capture_train_step(rollback=)`): BatchNorm running statistics, the sound bank and the call counters of the pair builder
+        and the anchor sampler - the forward has already run.  On its own a skip thus protects the weights; it does not protect
+        BatchNorm buffers from a non-finite *input*.
     history: capacity of the record ring; `read()` reports how many records were overwritten before it saw them.
     Data parallel: the guard runs behind the late all-reduce on the reduced arena, so the gradient rule and the coefficient are
     the same on every rank (the loss rule is not, see above); this is not exercised beyond one process."""

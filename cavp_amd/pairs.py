@@ -100,6 +100,14 @@ class PairBuilder:
         if self._state is not None:
             self._state[:2].copy_(torch.tensor([self._seed, 0], dtype=torch.int64))
 
+    def rollback_ranges(self, bank: bool = True):
+        """[(name, tensor, byte_offset, nbytes)]: the bytes a call mutates that are state - the sound bank (`bank=False` leaves it
+        out), the ring heads and {seed, offset} of the state block.  `bad_inputs` is a diagnostic and is not named: a rolled-back
+        call must not hide that its input was bad.  For cavp_amd.rollback.StepRollback.add()."""
+        state = self._ensure()
+        out = [("bank", self._bank, 0, self._bank.numel() * 4)] if bank else []
+        return out + [("head", self._head, 0, self._head.numel() * 4), ("state", state, 0, 16)]
+
     @property
     def bank_vault(self) -> torch.Tensor:
         """[K, S, A] in the reference's logical order (slot 0 = oldest), materialised from the ring: for tests and checkpoints."""

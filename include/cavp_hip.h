@@ -532,6 +532,40 @@ int cavp_optimizer_schedule_guarded(cavp_opt_state* state_device, cavp_guard_sta
 int cavp_optimizer_step_guarded(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum, float eps,
                                 const cavp_opt_state* state_device, const cavp_guard_state* guard_device, void* stream);
 
+/* Step rollback (added to ABI 16): a skipped step also undoes what its forward wrote.  A device-resident table of byte ranges, two
+ * launches whatever the number of ranges:
+ *   cavp_rollback_save:    live -> shadow for every range without CAVP_ROLLBACK_SCRUB;
+ *   cavp_rollback_restore: loads word_device[0] (the step guard's cavp_guard_state.skip; NULL = forced).  Zero: every workgroup returns
+ *                          after that one load.  Otherwise shadow -> live for every range, zeros into the CAVP_ROLLBACK_SCRUB ranges.
+ * A range is `nbytes` bytes (a multiple of 4) at any 4-byte aligned live / shadow address; copies are 16-byte vectors where the
+ * two addresses share their offset from a 16-byte boundary and the vector lies inside the range, dwords elsewhere; nothing outside
+ * [live, live + nbytes) and [shadow, shadow + nbytes) is read or written.  Live ranges must not overlap each other or a shadow.
+ * Work units: a range is cut into blocks of 1024 bytes on a grid that starts at the 16-byte boundary at or below `live`, that is
+ * cavp_rollback_blocks(live_address, nbytes) = ceil(((live_address & 15) + nbytes) / 1024) blocks; blk0 = the running sum over the
+ * preceding ranges (ascending), total_blocks = the sum over all.  A workgroup serves 16 consecutive blocks whatever ranges they belong
+ * to (many small ranges share one), the grid is min(ceil(total_blocks / 16), 2048) workgroups striding over the rest.
+ * The state block counts the launches that did something: saves, and restores whose word was set or that were forced (the only
+ * atomics).  nranges == 0 or total_blocks == 0: success, nothing launched, nothing counted. */
+typedef struct cavp_rollback_range {
+  void* live;
+  void* shadow;            /* NULL for a scrub range */
+  int64_t nbytes;
+  int32_t blk0;
+  int32_t flags;           /* CAVP_ROLLBACK_* */
+} cavp_rollback_range;
+#define CAVP_ROLLBACK_SCRUB 1   /* not saved; zero-filled by a restore that happens */
+typedef struct cavp_rollback_state {
+  int64_t saves;
+  int64_t restores;
+} cavp_rollback_state;
+int64_t cavp_rollback_range_bytes(void);
+int64_t cavp_rollback_state_bytes(void);
+int64_t cavp_rollback_blocks(int64_t live_address, int64_t nbytes);
+int cavp_rollback_save(const cavp_rollback_range* table_device, int32_t nranges, int32_t total_blocks,
+                       cavp_rollback_state* state_device, void* stream);
+int cavp_rollback_restore(const cavp_rollback_range* table_device, int32_t nranges, int32_t total_blocks,
+                          const int32_t* word_device, cavp_rollback_state* state_device, void* stream);
+
 /* ---- log-mel front-end = trainers' preprocess_audio (trainer_cavp_vpo_mono.py:43-52,59-69;
  * utils/sourcesep.py:23-47): STFT(n_fft 512, hop, centred window, reflect padding) -> |.|^2 -> mel filterbank ->
  * 20 log10(max(amin, x)) -> 2 (x - spec_min) / (spec_max - spec_min) - 1.

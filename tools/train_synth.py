@@ -12,7 +12,7 @@ shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
                                    [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]]
-                                   [--guard [--max-norm X]]] [--preview DIR]
+                                   [--guard [--max-norm X] [--rollback]]] [--preview DIR]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -36,6 +36,11 @@ cavp_amd.wave.WaveStage (resample to 16 kHz, centre crop to one second, channel 
 --guard (with --graph): a cavp_amd.optim.StepGuard on the recorded update - global gradient norm, --max-norm clipping, the whole
 update skipped when a gradient or a loss is not finite.  The loop then reads no loss back per step: every 5 steps one guard.read()
 returns the records written since (step, rate, both losses, gradient norm, coefficient, skipped / clipped) and they are printed.
+
+--rollback (with --guard): a cavp_amd.rollback.StepRollback over the model's BatchNorm state, the pair builder, the sampler and, with
+--augment, the frame augmentation, handed to both captures: a skipped step also undoes what its forward wrote, and the captures undo
+their own warm-up passes, so nothing is reloaded or reseeded behind them.  At the end the rollback's restore count is printed next to
+the guard's skipped count; the run fails if the two differ.
 
 --preview DIR: after training, the reference trainers' image upload (Tensorboard.upload_wandb_image) without its whole-tensor host
 copies: eval mode, model.predict on the last batch, cavp_amd.preview.PreviewStage on image, label and mask, one 5-byte-per-pixel copy,
@@ -78,6 +83,8 @@ def main():
     ap.add_argument("--guard", action="store_true", help="with --graph: StepGuard on the recorded update (gradient norm, non-finite skip); "
                     "the progress lines come from guard.read(), one synchronisation per 5 steps instead of .item() reads")
     ap.add_argument("--max-norm", type=float, default=None, help="with --guard: clip the global gradient norm to this bound")
+    ap.add_argument("--rollback", action="store_true", help="with --guard: a StepRollback over the model's BatchNorm state and every enabled "
+                    "stage, so a skipped step also undoes its forward; the capture then leaves no trace and nothing is reseeded")
     ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
     ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
     ap.add_argument("--raw-audio", action="store_true", help="with --augment: 44.1 kHz int16 stereo PCM through WaveStage at the head of the prologue")
@@ -95,6 +102,8 @@ def main():
         ap.error("--guard needs --graph: the guard lives beside the device schedule of the recorded update")
     if a.max_norm is not None and not a.guard:
         ap.error("--max-norm needs --guard")
+    if a.rollback and not a.guard:
+        ap.error("--rollback needs --guard: the guard's skip word decides the restore")
     if a.graph and not a.pairs:
         ap.error("--graph needs --from-waveform --contrast --pairs")
 
@@ -171,6 +180,7 @@ def main():
         return pcm, torch.randint(RAW_LEN // 2, RAW_LEN + 1, (B, 1), dtype=torch.int32, generator=g)
 
     replays = None
+    rb = None
     aug = None
     wave_stage = None
     if a.graph:
@@ -229,18 +239,27 @@ def main():
                 s_audio.copy_(front(built.waveforms))
                 s_shuf.copy_(built.label_shuffle)
             return prologue
+        if a.rollback:                                          # everything an iteration's forward mutates, through whatever is enabled
+            from cavp_amd.rollback import StepRollback
+            rb = StepRollback(dev).add_model(model).add(pairs).add(crit)
+            if aug is not None:
+                rb.add(aug)
+            rb.freeze()
         replays = []
         for ow in (False, True):
             rep = model.capture_train_step(s_image, s_audio, s_label, contrast=crit, label_shuffle=s_shuf,
-                                           contrast_weight=a.contrast_weight, optimizer=opt, prologue=prologue_of(ow))
+                                           contrast_weight=a.contrast_weight, optimizer=opt, prologue=prologue_of(ow),
+                                           **({"rollback": rb} if rb is not None else {}))
             replays.append((rep, model._last_losses))           # (each graph has its own static loss buffers)
-        # the warm-up passes of the captures ran the pair builder, the sampler and the BatchNorm statistics for real: start over
-        model.load_state_dict(start)
-        if aug is not None:
-            aug.manual_seed(1234 + rank)
-        pairs.manual_seed(1234 + rank)
-        pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
-        crit.manual_seed(1234 + rank)
+        if rb is None:
+            # the warm-up passes of the captures ran the pair builder, the sampler and the BatchNorm statistics for real: start over
+            # (with a rollback the captures undo their own passes and this is unnecessary)
+            model.load_state_dict(start)
+            if aug is not None:
+                aug.manual_seed(1234 + rank)
+            pairs.manual_seed(1234 + rank)
+            pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
+            crit.manual_seed(1234 + rank)
 
     for it in range(a.steps):
         if a.fixed_batch:
@@ -320,6 +339,13 @@ def main():
         dt = (time.time() - t0) / (a.steps - 2)
         print(f"{B * world / dt:.1f} frames/s over {world} GPU(s) ({dt * 1e3:.1f} ms/step incl. host-side input generation, "
               f"{'one graph replay' if a.graph else 'eager launches, optimiser step'})")
+    if rb is not None:
+        stats, skipped = rb.stats(), int(guard.last()["skipped_total"].item())
+        if rank == 0:
+            print(f"rollback: {stats['restores']} restores in {stats['saves']} iterations, the guard skipped {skipped} "
+                  f"({sum(rb.registered_bytes().values())} bytes registered: {rb.registered_bytes()})")
+        if stats["restores"] != skipped:
+            raise SystemExit("rollback: the restores and the guard's skipped steps disagree")
     if rank == 0 and pairs is not None:
         plan = pairs.last_plan()
         print(f"pairs, last step: {int(plan['if_match'].sum())} of {B} rows matched, {plan['n_overwritten']} taken from the sound bank "
