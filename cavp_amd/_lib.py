@@ -208,6 +208,11 @@ PROTOTYPES = {
     # ---- preview stage: x / y / y_tilde panels as bytes, optional NEAREST resize (added to ABI 16) ----
     "cavp_preview_panels": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "cavp_preview_resize": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    # ---- device store: resident data set, epoch sampler and batch gather (added to ABI 16) ----
+    "cavp_store_plan_words": (_i32, [_i32]),
+    "cavp_store_plan": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32,
+                               _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_store_gather": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1012,6 +1012,43 @@ int cavp_preview_panels(const float* image, const float* mean_std, const void* l
 int cavp_preview_resize(const uint8_t* src, uint8_t* dst, const int32_t* row_tab, const int32_t* col_tab, int32_t B, int32_t H,
                         int32_t W, int32_t Ho, int32_t Wo, int32_t has_x, int32_t has_y, void* stream);
 
+/* ---- Device store (three entry points added to ABI 16; nothing else changed): a frozen, device-resident ragged data set, the
+ * sampler of the reference's loaders (RandomSampler / DistributedSampler with drop_last=True, main_vpo_mono.py:188-201) and the
+ * gather of one batch into the staging buffers of the frame augmentation and the wave stage, restated in tests/_store_ref.py ----
+ * The store: N items packed back to back, no padding, in three byte arenas - frames (item i: [h][w][3] u8 at frame_off[i]), masks
+ * ([h][w] u8 at mask_off[i]) and PCM (source s of item i: [n_ch][length] samples of `elem` bytes, 2 = int16 or 4 = float32, at
+ * pcm_off[i][s]) - with int64 byte-offset tables frame_off [N], mask_off [N], pcm_off [N][S] and int32 size [N][2] = (h, w),
+ * n_src [N], length / rate_idx / n_ch [N][S].  1 <= h <= Hs, 1 <= w <= Ws, 0 <= n_src <= S, 1 <= length <= Lmax, 1 <= n_ch <= Cm.
+ * cavp_store_plan, one workgroup: row i < B of step t = state[1] (state: int64 [4], device, persistent, {seed, t, bad_inputs,
+ *   reserved}) takes the item index_in[i] when index_in != NULL (an entry outside [0, N) adds 1 to state[2] and becomes 0), else
+ *   M = ceil(N / world), spe = M / B (>= 1), e = t / spe, j = (t % spe) * B + i, q = j * world + rank, q -= N if q >= N, item =
+ *   pi_e(q): a balanced Feistel network on 2k bits, bits = max(2, bit_length(N - 1)), k = ceil(bits / 2), x = (L << k) | R, 8 rounds
+ *   r = 0 .. 7 of (L, R) <- (R, L ^ (f & (2^k - 1))), f = word 0 of Philox4x32-10 at counter (R, r, e_lo, e_hi) under the key
+ *   (seed_lo, seed_hi); the whole network is applied again until x < N.  No sort, no stored permutation.
+ *   Writes index [B], sizes [B][2], length / n_ch [B][S] (0 for the sources >= n_src), rate_idx [B][S] (present sources only) and
+ *   the int64 plan [B][cavp_store_plan_words(S) = 4 + 3 S] = {frame_off, mask_off, h, w, then per source {pcm_off, length, n_ch}},
+ *   then state[1] = t + 1 - with or without index_in; the only writer of t.  A table entry that leaves its limits or its arena
+ *   (frame_bytes, mask_bytes, pcm_bytes) is counted in state[2] and planned as empty: nothing is read out of bounds.
+ * cavp_store_gather, after the plan on the same stream, grid (x, B, 2 + S * Cm): the item's h x w window into out_frames
+ *   [B][Hs][Ws][3] and out_masks [B][Hs][Ws] (top-left), channel c < n_ch of source s into out_pcm [B][S][Cm][Lmax] up to length.
+ *   Outside the windows, beyond length and in absent channels and sources NOTHING is written.  A row (3w / w / length * elem
+ *   bytes; the whole window as one row when w == Ws) is copied as a byte-wise head up to the destination's 16-byte boundary, a
+ *   body of 16-byte stores fed by unaligned 16-byte loads, and a byte-wise tail; every access lies inside the row, so no byte
+ *   outside an arena is read whatever the last item's alignment.  Work items are (row, 4 KiB chunk) pairs, one wave each.
+ * B <= 1024, Hs, Ws <= CAVP_STORE_MAX_STAGE, Lmax <= 2^28, 2 + S * Cm <= 65535, world <= N, ceil(N / world) >= B.
+ * No allocation, no synchronisation, no host read of a device value: capturable in a hipGraph. */
+#define CAVP_STORE_MAX_STAGE 16384
+int cavp_store_plan_words(int32_t S);
+int cavp_store_plan(const int64_t* frame_off, const int64_t* mask_off, const int32_t* size, const int32_t* n_src,
+                    const int64_t* pcm_off, const int32_t* length, const int32_t* rate_idx, const int32_t* n_ch, int64_t frame_bytes,
+                    int64_t mask_bytes, int64_t pcm_bytes, int32_t N, int32_t B, int32_t S, int32_t Hs, int32_t Ws, int32_t Cm,
+                    int64_t Lmax, int32_t elem, int32_t rank, int32_t world, const int32_t* index_in, int64_t* state,
+                    int32_t* out_index, int32_t* out_sizes, int32_t* out_length, int32_t* out_rate_idx, int32_t* out_n_ch,
+                    int64_t* plan, void* stream);
+int cavp_store_gather(const uint8_t* frames, const uint8_t* masks, const uint8_t* pcm, const int64_t* plan, int32_t B, int32_t S,
+                      int32_t Hs, int32_t Ws, int32_t Cm, int64_t Lmax, int32_t elem, uint8_t* out_frames, uint8_t* out_masks,
+                      uint8_t* out_pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,8 @@ There is no dataset here (no network): images / waveforms / labels are seeded ra
 shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
-                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]]
-                                   [--guard [--max-norm X] [--rollback]]] [--preview DIR]
+                                   [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]
+                                   [--resident [--store-items N]]] [--guard [--max-norm X] [--rollback]]] [--preview DIR]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -32,6 +32,12 @@ image labels the pair builder sees are computed on the device from the augmented
 compute them after their transform.  --resize: the AVSS set-ups' variant (the AVS scale list, no jitter, a resize to --hw instead
 of pad + crop).  --raw-audio: the clips are raw material too - 10 s of synthetic 44.1 kHz int16 stereo PCM per row - and
 cavp_amd.wave.WaveStage (resample to 16 kHz, centre crop to one second, channel mean) stands at the head of the prologue.
+
+--resident (with --augment): the raw material is a data set that lives on the device - --store-items synthetic items (frame, mask and,
+with --raw-audio, one PCM clip each) are appended to a cavp_amd.store.DeviceStore once, and BatchFeeder.feed stands at the head of the
+prologue: the sampler (RandomSampler / DistributedSampler semantics, one shared store and a rank of its own per process) and the gather
+into the staging buffers are two more launches of the graph, and the loop body is replay() - no host draw, no host copy.  (Without
+--raw-audio the 16 kHz clip is still drawn and copied by the host.)
 
 --guard (with --graph): a cavp_amd.optim.StepGuard on the recorded update - global gradient norm, --max-norm clipping, the whole
 update skipped when a gradient or a loss is not finite.  The loop then reads no loss back per step: every 5 steps one guard.read()
@@ -88,10 +94,17 @@ def main():
     ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
     ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
     ap.add_argument("--raw-audio", action="store_true", help="with --augment: 44.1 kHz int16 stereo PCM through WaveStage at the head of the prologue")
+    ap.add_argument("--resident", action="store_true", help="with --augment: frames, masks and (with --raw-audio) PCM come from a device-resident "
+                    "DeviceStore through BatchFeeder.feed at the head of the prologue; the loop body is replay()")
+    ap.add_argument("--store-items", type=int, default=None, help="with --resident: items in the store (default 4 x --batch x world)")
     ap.add_argument("--preview", metavar="DIR", default=None, help="after training: x / y / y_tilde PNGs of the last batch through PreviewStage")
     a = ap.parse_args()
     if a.raw_audio and not a.augment:
         ap.error("--raw-audio needs --augment")
+    if a.resident and not a.augment:
+        ap.error("--resident needs --augment (with --graph)")
+    if a.store_items is not None and not a.resident:
+        ap.error("--store-items needs --resident")
     if a.augment and not a.graph:
         ap.error("--augment needs --graph (with --from-waveform --contrast --pairs)")
     if a.resize and not a.augment:
@@ -179,10 +192,31 @@ def main():
         pcm = torch.randint(-3277, 3278, (B, 1, 2, RAW_LEN), dtype=torch.int16, generator=g)
         return pcm, torch.randint(RAW_LEN // 2, RAW_LEN + 1, (B, 1), dtype=torch.int32, generator=g)
 
+    def build_store(stage, n_items):
+        """n_items synthetic items of draw_raw_batch's / draw_raw_audio's kind in a frozen DeviceStore - the same store on every rank"""
+        from cavp_amd.store import DeviceStore
+        gs = torch.Generator().manual_seed(4321)
+        store = DeviceStore(stage=stage, max_sources=1, max_channels=2, max_len=RAW_LEN if a.raw_audio else 1, pcm_dtype=torch.int16,
+                            device=dev)
+        for _ in range(n_items):
+            frame = torch.randint(0, 256, stage + (3,), dtype=torch.uint8, generator=gs)
+            mask = torch.zeros(stage, dtype=torch.uint8)
+            for _ in range(1 + int(torch.rand((), generator=gs) < 0.25)):
+                c = int(torch.randint(1, pairs.K, (), generator=gs))
+                y, x = (int(torch.randint(0, stage[k] // 2, (), generator=gs)) for k in (0, 1))
+                mask[y:y + stage[0] // 3, x:x + stage[1] // 3] = RAW0 + c
+            sources = []
+            if a.raw_audio:
+                n = int(torch.randint(RAW_LEN // 2, RAW_LEN + 1, (), generator=gs))
+                sources.append((torch.randint(-3277, 3278, (2, n), dtype=torch.int16, generator=gs), 0))
+            store.append(frame, mask, sources)
+        return store.freeze()
+
     replays = None
     rb = None
     aug = None
     wave_stage = None
+    feeder = None
     if a.graph:
         from cavp_amd.pairs import PairResult
         s_image = torch.zeros(B, 3, a.hw, a.hw, device=dev)
@@ -215,6 +249,12 @@ def main():
             s_masks = torch.zeros((B,) + stage, dtype=torch.uint8, device=dev)
             s_sizes = torch.tensor([list(stage)] * B, dtype=torch.int32, device=dev)
             augmented, labelled = AugResult(B, (a.hw, a.hw), dev), LabelResult(B, pairs.K, (a.hw, a.hw), dev, True)
+            if a.resident:                                      # the staging buffers are the feeder's: nothing is copied into them from here
+                from cavp_amd.store import BatchFeeder, FeedResult
+                store = build_store(stage, a.store_items if a.store_items is not None else 4 * B * world)
+                feeder = BatchFeeder(store, batch=B, seed=1234, rank=rank, world=world)
+                fed = FeedResult(B, store, dev)
+                s_frames, s_masks, s_sizes = fed.frames, fed.masks, fed.sizes
         if a.raw_audio:
             from cavp_amd.wave import WaveResult, WaveStage
             wave_stage = WaveStage(audio_len=hyp.audio_len, rates=(RAW_RATE,), max_sources=1, max_channels=2, max_len=RAW_LEN,
@@ -224,9 +264,13 @@ def main():
             s_rate_idx = torch.zeros((B, 1), dtype=torch.int32, device=dev)
             s_n_ch = torch.full((B, 1), 2, dtype=torch.int32, device=dev)
             cut = WaveResult(B, 16000, dev)
+            if feeder is not None:
+                s_pcm, s_pcm_len, s_rate_idx, s_n_ch = fed.pcm, fed.length, fed.rate_idx, fed.n_ch
 
         def prologue_of(overwrite):
             def prologue():
+                if feeder is not None:     # sampler + gather: this step's items into the staging buffers the two stages below read
+                    feeder.feed(out=fed)
                 if aug is not None:        # raw frames -> image, label -> remapped label, img_label: nothing returns to the host
                     aug(s_frames, s_masks, s_sizes, out=augmented)
                     stage_labels(augmented.label, out=labelled)
@@ -244,6 +288,8 @@ def main():
             rb = StepRollback(dev).add_model(model).add(pairs).add(crit)
             if aug is not None:
                 rb.add(aug)
+            if feeder is not None:
+                rb.add(feeder)                                  # a skipped step sees the same batch again
             rb.freeze()
         replays = []
         for ow in (False, True):
@@ -257,6 +303,8 @@ def main():
             model.load_state_dict(start)
             if aug is not None:
                 aug.manual_seed(1234 + rank)
+            if feeder is not None:
+                feeder.set_step(0)
             pairs.manual_seed(1234 + rank)
             pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
             crit.manual_seed(1234 + rank)
@@ -264,11 +312,20 @@ def main():
     for it in range(a.steps):
         if a.fixed_batch:
             g = torch.Generator().manual_seed(1234 + rank)      # the same batch every step
-        image = torch.randn(B, 3, a.hw, a.hw, generator=g)
-        label = torch.randint(0, a.num_classes, (B, a.hw, a.hw), generator=g)
+        if feeder is not None:                                  # resident: the batch is drawn and gathered inside the graph
+            if a.fixed_batch:
+                feeder.set_step(0)
+            if wave_stage is None:
+                s_wave.copy_(draw_pairs_batch()[0])
+        else:
+            image = torch.randn(B, 3, a.hw, a.hw, generator=g)
+            label = torch.randint(0, a.num_classes, (B, a.hw, a.hw), generator=g)
         if replays is not None:                                 # copy the batch in, replay: nothing else is launched from here
-            wave, img_label = draw_pairs_batch()
-            if aug is not None:                                 # raw material only: image, label and img_label come from the prologue
+            if feeder is None:
+                wave, img_label = draw_pairs_batch()
+            if feeder is not None:
+                pass                                            # resident: nothing to draw, nothing to copy
+            elif aug is not None:                               # raw material only: image, label and img_label come from the prologue
                 frames, masks = draw_raw_batch(tuple(s_masks.shape[1:]))
                 for dst, src in ((s_frames, frames), (s_masks, masks), (s_wave, wave)):
                     dst.copy_(src)
@@ -355,6 +412,10 @@ def main():
         stage_labels.check()
         print(f"input chain: {'resize' if a.resize else 'pad + crop'} augmentation, img_label from the augmented mask: "
               f"{labelled.img_label[:, 1:].sum(0).tolist()} frames per foreground class in the last batch")
+    if rank == 0 and feeder is not None:
+        feeder.check()
+        print(f"resident: {len(store)} items, {store.nbytes / 1e6:.1f} MB on the device ({store.arena_bytes()}); step {feeder.step()} = epoch "
+              f"{feeder.epoch_of(feeder.step())} of {feeder.steps_per_epoch} steps; items of the last batch {fed.index[:8].tolist()} ...")
     if rank == 0 and wave_stage is not None:
         wave_stage.check()
         print(f"raw audio: {RAW_LEN / RAW_RATE:.0f} s of {RAW_RATE} Hz int16 stereo per row -> [B, 1, 16000] by WaveStage; rms of the last batch "
