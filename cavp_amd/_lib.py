@@ -213,6 +213,11 @@ PROTOTYPES = {
     "cavp_store_plan": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32,
                                _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cavp_store_gather": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    # ---- clip store: resident T-frame clips, frame draw, in-order eval walk, clip gather (added to ABI 16) ----
+    "cavp_clips_plan_words": (_i32, [_i32, _i32]),
+    "cavp_clips_plan_train": (_i32, [_vp] * 13 + [_i64] * 3 + [_i32] * 8 + [_i64] + [_i32] * 3 + [_vp] * 12),
+    "cavp_clips_plan_eval": (_i32, [_vp] * 13 + [_i64] * 3 + [_i32] * 8 + [_i64] + [_i32] * 3 + [_vp] * 11),
+    "cavp_clips_gather": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

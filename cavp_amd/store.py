@@ -351,3 +351,14 @@ class BatchFeeder:
                                          st.Cm, st.Lmax, st.elem, _ptr(out.frames), _ptr(out.masks), _ptr(out.pcm), stream),
                    "cavp_store_gather")
         return out
+
+
+_CLIP_NAMES = ("ClipStore", "ClipFeeder", "ClipFeedResult", "ClipEvalResult")
+
+
+def __getattr__(name):
+    """The clip store (cavp_amd/clips.py) is re-exported from here; resolved on first use, since clips.py builds on this module."""
+    if name in _CLIP_NAMES:
+        from . import clips
+        return getattr(clips, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1049,6 +1049,71 @@ int cavp_store_gather(const uint8_t* frames, const uint8_t* masks, const uint8_t
                       int32_t Hs, int32_t Ws, int32_t Cm, int64_t Lmax, int32_t elem, uint8_t* out_frames, uint8_t* out_masks,
                       uint8_t* out_pcm, void* stream);
 
+/* ---- Clip store (four entry points added to ABI 16; nothing else changed): the device store for data sets whose items are clips
+ * of up to 32 frames (the reference's S4Dataset / MS3Dataset / AVSS VisualDataset), the frame draw of the clip trainers
+ * (trainer_cavp_avs_obj.py:162-172) and the in-order walk of their validation loops, restated in tests/_clips_ref.py ----
+ * The store: the three byte arenas of the device store, packed back to back, no padding.  Frame tables over all F frames of all
+ * clips: int64 frame_off [F] ([h][w][3] u8 there), int64 mask_off [F] ([h][w] u8 there; -1 = the frame has no mask and takes no
+ * byte of the mask arena), int32 size [F][2] = (h, w), 1 <= h <= Hs, 1 <= w <= Ws.  Clip tables over the N clips: int32 first [N]
+ * (the clip's frame k is frame first + k of the frame tables), int32 n_frames [N] (1 .. Tmax, Tmax <= 32), uint32 avail [N] (bit k
+ * set: a training draw may take frame k; non-zero, no bit >= n_frames, every named frame has a mask), int32 mask_num [N]
+ * (0 .. n_frames), int32 tag [N] (the caller's, passed through), and the device store's PCM tables with one row per clip: int32
+ * n_src [N], int64 pcm_off [N][S], int32 length / rate_idx / n_ch [N][S].
+ * state: int64 [4], device, persistent, {seed, t_train, bad_inputs, t_eval}.  cavp_clips_plan_train reads and writes t_train only,
+ *   cavp_clips_plan_eval t_eval only; both add to bad_inputs.
+ * cavp_clips_plan_train, one workgroup, one thread per row: row i < B of step t = state[1].
+ *   Clip: exactly the item rule of cavp_store_plan (index_in[i], an entry outside [0, N) adds 1 to state[2] and becomes 0; else
+ *   pi_e(q) with M, spe, e, j, q as there).
+ *   Frame: frame_in[i] when frame_in != NULL; a value that is not a set bit of avail (negative and >= 32 included) adds 1 to
+ *   state[2] and becomes the lowest set bit.  Else n = popcount(avail), w = word 0 of Philox4x32-10 at counter (i, 0xC11F, t_lo,
+ *   t_hi) under the key (seed_lo, seed_hi) (t with or without index_in; a Feistel counter has c1 < 8, so the two never meet),
+ *   r = (uint64(w) * n) >> 32, frame = the position of the r-th (0-based, from bit 0) set bit of avail.
+ *   Writes index [B] (the clip), select [B] (the frame), tag [B], sizes [B][2] (the frame's h, w), length / n_ch [B][S] (0 for the
+ *   sources >= n_src), rate_idx [B][S] (present sources only), the int64 plan [B][cavp_clips_plan_words(1, S)] and then state[1] =
+ *   t + 1.
+ * cavp_clips_plan_eval, one workgroup, one thread per (row, frame slot): in order, no shuffle.  M = ceil(N / world), P = ceil(M / B)
+ *   steps per pass; step t = state[3] has s = t mod P; row i has q = (s * B + i) * world + rank.  q < N: clip q, index[i] = q,
+ *   count[i] = mask_num[q].  q >= N: a padding row - everything below as for clip 0, but index[i] = -1 and count[i] = 0.  Over the P
+ *   steps of a pass and all ranks every clip is a non-padding row exactly once.
+ *   Writes index, count, n_frames, tag [B], sizes [B * Tmax][2] (slot k < n_frames: the frame's h, w; slot k >= n_frames: the h, w
+ *   of the clip's frame 0), length / rate_idx / n_ch as above, the int64 plan [B][cavp_clips_plan_words(Tmax, S)], then state[3] =
+ *   t + 1.
+ * The plan row: int64 [4 T_out + 3 S] = T_out x {frame_off, mask_off, h, w} (T_out = 1 for train, Tmax for eval; an empty slot has
+ *   h = w = 0, a frame without a mask mask_off = -1), then per source {pcm_off, length, n_ch}.
+ * Both plans check every table value on the device as cavp_store_plan does: a clip whose first / n_frames / avail leave their
+ *   limits, a frame whose size or offsets leave the stage or an arena (train: or that has no mask), a mask_num outside
+ *   [0, n_frames] (count becomes 0), a source outside its limits - each adds 1 to state[2] and is planned as empty (sizes 0, 0).
+ * cavp_clips_gather, after either plan on the same stream, grid (x, B, 2 T_out + S * Cm): z < T_out the frame of slot z, z < 2 T_out
+ *   the mask of slot z - T_out, then channel c of source s at z = 2 T_out + s * Cm + c.  Slot k of row b goes to out_frames
+ *   [B][T_out][Hs][Ws][3] and out_masks [B][T_out][Hs][Ws] (top-left h x w window), channel c < n_ch of source s to out_pcm
+ *   [B][S][Cm][Lmax] up to length.  An empty slot, the mask of a frame without one, absent channels and sources, and every byte
+ *   outside the windows: NOTHING is written.  Rows are copied by the device store's row copy (byte head to the destination's
+ *   16-byte boundary, 16-byte stores fed by unaligned 16-byte loads, byte tail, no access outside the row).
+ * B <= 1024, B * T_out <= 1024, Tmax <= 32, 2 T_out + S * Cm <= 65535 (beyond: CAVP_ERR_UNSUPPORTED), Hs, Ws <=
+ * CAVP_STORE_MAX_STAGE, Lmax <= 2^28, world <= N, and for the train plan ceil(N / world) >= B.
+ * No allocation, no synchronisation, no host read of a device value: capturable in a hipGraph. */
+#define CAVP_CLIPS_MAX_FRAMES 32
+int cavp_clips_plan_words(int32_t T_out, int32_t S);
+int cavp_clips_plan_train(const int64_t* frame_off, const int64_t* mask_off, const int32_t* size, const int32_t* first,
+                          const int32_t* n_frames, const uint32_t* avail, const int32_t* mask_num, const int32_t* tag,
+                          const int32_t* n_src, const int64_t* pcm_off, const int32_t* length, const int32_t* rate_idx,
+                          const int32_t* n_ch, int64_t frame_bytes, int64_t mask_bytes, int64_t pcm_bytes, int32_t F, int32_t N,
+                          int32_t B, int32_t S, int32_t Tmax, int32_t Hs, int32_t Ws, int32_t Cm, int64_t Lmax, int32_t elem,
+                          int32_t rank, int32_t world, const int32_t* index_in, const int32_t* frame_in, int64_t* state,
+                          int32_t* out_index, int32_t* out_select, int32_t* out_tag, int32_t* out_sizes, int32_t* out_length,
+                          int32_t* out_rate_idx, int32_t* out_n_ch, int64_t* plan, void* stream);
+int cavp_clips_plan_eval(const int64_t* frame_off, const int64_t* mask_off, const int32_t* size, const int32_t* first,
+                         const int32_t* n_frames, const uint32_t* avail, const int32_t* mask_num, const int32_t* tag,
+                         const int32_t* n_src, const int64_t* pcm_off, const int32_t* length, const int32_t* rate_idx,
+                         const int32_t* n_ch, int64_t frame_bytes, int64_t mask_bytes, int64_t pcm_bytes, int32_t F, int32_t N,
+                         int32_t B, int32_t S, int32_t Tmax, int32_t Hs, int32_t Ws, int32_t Cm, int64_t Lmax, int32_t elem,
+                         int32_t rank, int32_t world, int64_t* state, int32_t* out_index, int32_t* out_count, int32_t* out_n_frames,
+                         int32_t* out_tag, int32_t* out_sizes, int32_t* out_length, int32_t* out_rate_idx, int32_t* out_n_ch,
+                         int64_t* plan, void* stream);
+int cavp_clips_gather(const uint8_t* frames, const uint8_t* masks, const uint8_t* pcm, const int64_t* plan, int32_t B, int32_t T_out,
+                      int32_t S, int32_t Hs, int32_t Ws, int32_t Cm, int64_t Lmax, int32_t elem, uint8_t* out_frames,
+                      uint8_t* out_masks, uint8_t* out_pcm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,16 @@ of 3 w bytes at arbitrary alignment).  The four routes alternate inside each of 
 the bytes gathered per call and per second are reported next to the chip's measured float4 copy rate (6.29 TB/s, read plus written
 bytes: compare it with `traffic_TBps` = 2 x gathered bytes per second).  That is a reference point, not a target.
 
-    python tools/bench_store.py [--batch 32] [--items 64] [--rounds 5] [--host-iters 3] [--feed-iters 200] [--step] [--out FILE]
+  --clips T     instead of the above: the clip store (cavp_amd.clips: ClipStore + ClipFeeder) beside the single-frame store in one
+                process.  Clip i holds T frames of item i's size (its frame 0 IS item i's frame) and item i's PCM, so ClipFeeder.feed
+                gathers what BatchFeeder.feed gathers - the same bytes per batch, plus one Philox call per row in the plan - and
+                feed_clips gathers T frames and masks per row.  feed / clip_feed / clip_eval, eager and captured, alternate inside
+                each round; per store kind the record holds the medians, `clip_feed_over_feed` (ratio of the medians) next to
+                `feed_round_spread` ((max - min) / median of feed's own rounds), and for the eval feed the read-plus-written rate
+                against the same copy-rate figure.
+
+    python tools/bench_store.py [--batch 32] [--items 64] [--rounds 5] [--host-iters 3] [--feed-iters 200] [--step | --clips T]
+                                [--out FILE]
 
 One JSON line per run is appended to --out (default profiles/store_bench.jsonl).  Needs a GPU; there is no fallback."""
 import argparse
@@ -148,6 +157,79 @@ def bench_routes(a, dev):
     return rec
 
 
+def make_clip_store(items, T, dev):
+    """Clip i: T frames of item i's size (frame 0 is item i's, the others are rolled copies: the content does not matter here), a mask
+    on every frame, item i's PCM."""
+    from cavp_amd.clips import ClipStore
+    st = ClipStore(stage=STAGE, max_frames=T, max_sources=1, max_channels=2, max_len=RAW_LEN, pcm_dtype=torch.int16, device=dev)
+    for f, m, p in items:
+        st.append([torch.roll(f, k, 0) for k in range(T)], [torch.roll(m, k, 0) for k in range(T)], [(p, 0)])
+    return st.freeze()
+
+
+def capture(fn):
+    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    return graph
+
+
+def bench_clips(a, dev):
+    """The train and the eval clip feed against feed() on a single-frame store of the same items, alternating inside each round."""
+    from cavp_amd.clips import ClipEvalResult, ClipFeeder, ClipFeedResult
+    from cavp_amd.store import BatchFeeder, FeedResult
+    B, T = a.batch, a.clips
+    rec = {}
+    for kind in ("full", "ragged"):
+        items = make_items(a.items, kind == "ragged")
+        store, cstore = make_store(items, dev), make_clip_store(items, T, dev)
+        feeder, cfeeder = BatchFeeder(store, batch=B, seed=1), ClipFeeder(cstore, batch=B, seed=1)
+        res, cres, ev = FeedResult(B, store, dev), ClipFeedResult(B, cstore, dev), ClipEvalResult(B, cstore, dev)
+        fns = {"feed": lambda: feeder.feed(out=res), "clip_feed": lambda: cfeeder.feed(out=cres), "clip_eval": lambda: cfeeder.feed_clips(out=ev)}
+        for f in fns.values():              # the code objects are loaded outside the captures
+            f()
+        routes = {}
+        for k, f in fns.items():
+            routes[k + "_eager"] = f
+            routes[k + "_graph"] = capture(f).replay
+        for f in routes.values():
+            f()
+        torch.cuda.synchronize()
+        times = {k: [] for k in routes}
+        for _ in range(a.rounds):
+            for k, f in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.feed_iters):
+                    f()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) / a.feed_iters * 1e3)
+        feeder.check()
+        cfeeder.check()
+        out = {k: med(v) for k, v in times.items()}
+        n = len(items)
+        train_bytes = sum(item_bytes(it) for it in items) / n * B
+        eval_bytes = sum(T * (it[0].numel() + it[1].numel()) + 2 * it[2].numel() for it in items) / n * B
+        for k, nbytes in (("feed", train_bytes), ("clip_feed", train_bytes), ("clip_eval", eval_bytes)):
+            for mode in ("_eager", "_graph"):
+                sec = out[k + mode]["ms_median"] * 1e-3
+                out[k + mode].update({"traffic_TBps": round(2 * nbytes / sec / 1e12, 3),
+                                      "share_of_copy_rate": round(2 * nbytes / sec / 1e12 / COPY_RATE_TBPS, 3)})
+        for mode in ("eager", "graph"):
+            f = out[f"feed_{mode}"]
+            out[f"clip_feed_over_feed_{mode}"] = round(out[f"clip_feed_{mode}"]["ms_median"] / f["ms_median"], 4)
+            out[f"feed_round_spread_{mode}"] = round((f["ms_max"] - f["ms_min"]) / f["ms_median"], 4)
+        out.update({"bytes_per_batch": int(train_bytes), "eval_bytes_per_batch": int(eval_bytes), "store_bytes": store.nbytes,
+                    "clip_store_bytes": cstore.nbytes, "items": n, "steps_per_epoch": cfeeder.steps_per_epoch,
+                    "steps_per_pass": cfeeder.steps_per_pass})
+        rec[kind] = out
+        del store, cstore, feeder, cfeeder, res, cres, ev, routes, fns
+    return rec
+
+
 def bench_step(a, dev):
     """The captured training step with and without the feeder at the head of its prologue, replayed alternately."""
     from cavp_amd.audio_frontend import MelFrontEnd
@@ -259,6 +341,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--step", action="store_true", help="also time the captured training step with and without the resident store")
     ap.add_argument("--step-iters", type=int, default=20)
+    ap.add_argument("--clips", type=int, default=None, metavar="T", help="the clip store's train and eval feed against feed(), T frames per clip")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "store_bench.jsonl"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -268,9 +351,15 @@ def main():
     dev = torch.device("cuda", 0)
     rec = {"bench": "store", "device": torch.cuda.get_device_name(0), "batch": a.batch, "stage": list(STAGE), "raw_len": RAW_LEN,
            "rounds": a.rounds, "host_iters": a.host_iters, "feed_iters": a.feed_iters, "copy_rate_TBps": COPY_RATE_TBPS}
-    rec.update(bench_routes(a, dev))
-    if a.step:
-        rec["step"] = bench_step(a, dev)
+    if a.clips is not None:
+        if a.step or not 1 <= a.clips <= 32 or a.batch * a.clips > 1024:
+            raise SystemExit("--clips T: 1 <= T <= 32, batch * T <= 1024, and not together with --step")
+        rec.update({"bench": "store_clips", "clips": a.clips})
+        rec.update(bench_clips(a, dev))
+    else:
+        rec.update(bench_routes(a, dev))
+        if a.step:
+            rec["step"] = bench_step(a, dev)
     line = json.dumps(rec)
     print(line, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -12,7 +12,8 @@ shapes; the point is the plumbing and its throughput, not accuracy.
 
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
                                    [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]
-                                   [--resident [--store-items N]]] [--guard [--max-norm X] [--rollback]]] [--preview DIR]
+                                   [--resident [--store-items N] [--clips T [--validate-every K]]]]
+                                   [--guard [--max-norm X] [--rollback]]] [--preview DIR]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -38,6 +39,14 @@ with --raw-audio, one PCM clip each) are appended to a cavp_amd.store.DeviceStor
 prologue: the sampler (RandomSampler / DistributedSampler semantics, one shared store and a rank of its own per process) and the gather
 into the staging buffers are two more launches of the graph, and the loop body is replay() - no host draw, no host copy.  (Without
 --raw-audio the 16 kHz clip is still drawn and copied by the host.)
+
+--clips T (with --resident): the items are clips, as in the AVSBench / AVSS data sets - T frames (the last one without a mask in
+every third clip) and, with --raw-audio, one PCM clip each in a cavp_amd.clips.ClipStore.  ClipFeeder.feed draws the clip and one
+of its frames on the device and gathers only that frame; the chain is ClipFeeder.feed -> FrameAugment -> LabelStage ->
+WaveStage(segments=T, select=fed.select) -> PairBuilder -> MelFrontEnd, all inside the captured prologue (the wave stage then
+crops T seconds and keeps the drawn frame's second).  --validate-every K (with --clips and --raw-audio): after every K steps one
+validation pass over the store - feed_clips -> FrameAugment.eval_ -> LabelStage -> WaveStage (all T segments) -> MelFrontEnd ->
+model.predict -> ClipValidation.update, batch // T clips per step, nothing copied to the host - and its ten numbers are printed.
 
 --guard (with --graph): a cavp_amd.optim.StepGuard on the recorded update - global gradient norm, --max-norm clipping, the whole
 update skipped when a gradient or a loss is not finite.  The loop then reads no loss back per step: every 5 steps one guard.read()
@@ -97,6 +106,10 @@ def main():
     ap.add_argument("--resident", action="store_true", help="with --augment: frames, masks and (with --raw-audio) PCM come from a device-resident "
                     "DeviceStore through BatchFeeder.feed at the head of the prologue; the loop body is replay()")
     ap.add_argument("--store-items", type=int, default=None, help="with --resident: items in the store (default 4 x --batch x world)")
+    ap.add_argument("--clips", type=int, default=None, metavar="T", help="with --resident: the store is a ClipStore of T-frame clips; "
+                    "ClipFeeder.feed draws clip and frame on the device")
+    ap.add_argument("--validate-every", type=int, default=None, metavar="K", help="with --clips and --raw-audio: a validation pass "
+                    "(feed_clips -> eval_ -> predict -> ClipValidation) after every K steps")
     ap.add_argument("--preview", metavar="DIR", default=None, help="after training: x / y / y_tilde PNGs of the last batch through PreviewStage")
     a = ap.parse_args()
     if a.raw_audio and not a.augment:
@@ -105,6 +118,10 @@ def main():
         ap.error("--resident needs --augment (with --graph)")
     if a.store_items is not None and not a.resident:
         ap.error("--store-items needs --resident")
+    if a.clips is not None and (not a.resident or not 1 <= a.clips <= 32 or a.batch < a.clips):
+        ap.error("--clips T needs --resident, 1 <= T <= 32 and --batch >= T")
+    if a.validate_every is not None and (a.clips is None or not a.raw_audio or a.validate_every < 1):
+        ap.error("--validate-every K needs --clips and --raw-audio, K >= 1")
     if a.augment and not a.graph:
         ap.error("--augment needs --graph (with --from-waveform --contrast --pairs)")
     if a.resize and not a.augment:
@@ -212,6 +229,32 @@ def main():
             store.append(frame, mask, sources)
         return store.freeze()
 
+    def build_clip_store(stage, n_clips, T):
+        """n_clips synthetic T-frame clips in a frozen ClipStore - the same store on every rank.  Every third clip has no mask on
+        its last frame (T > 1), as the AVSS sets have frames beyond mask_num."""
+        from cavp_amd.clips import ClipStore
+        gs = torch.Generator().manual_seed(4321)
+        store = ClipStore(stage=stage, max_frames=T, max_sources=1, max_channels=2, max_len=RAW_LEN if a.raw_audio else 1,
+                          pcm_dtype=torch.int16, device=dev)
+        for i in range(n_clips):
+            frames, masks = [], []
+            for k in range(T):
+                frames.append(torch.randint(0, 256, stage + (3,), dtype=torch.uint8, generator=gs))
+                mask = torch.zeros(stage, dtype=torch.uint8)
+                for _ in range(1 + int(torch.rand((), generator=gs) < 0.25)):
+                    c = int(torch.randint(1, pairs.K, (), generator=gs))
+                    y, x = (int(torch.randint(0, stage[j] // 2, (), generator=gs)) for j in (0, 1))
+                    mask[y:y + stage[0] // 3, x:x + stage[1] // 3] = RAW0 + c
+                masks.append(mask)
+            if T > 1 and i % 3 == 2:
+                masks.pop()
+            sources = []
+            if a.raw_audio:
+                n = int(torch.randint(RAW_LEN // 2, RAW_LEN + 1, (), generator=gs))
+                sources.append((torch.randint(-3277, 3278, (2, n), dtype=torch.int16, generator=gs), 0))
+            store.append(frames, masks, sources, tag=i % pairs.K)
+        return store.freeze()
+
     replays = None
     rb = None
     aug = None
@@ -250,15 +293,24 @@ def main():
             s_sizes = torch.tensor([list(stage)] * B, dtype=torch.int32, device=dev)
             augmented, labelled = AugResult(B, (a.hw, a.hw), dev), LabelResult(B, pairs.K, (a.hw, a.hw), dev, True)
             if a.resident:                                      # the staging buffers are the feeder's: nothing is copied into them from here
-                from cavp_amd.store import BatchFeeder, FeedResult
-                store = build_store(stage, a.store_items if a.store_items is not None else 4 * B * world)
-                feeder = BatchFeeder(store, batch=B, seed=1234, rank=rank, world=world)
-                fed = FeedResult(B, store, dev)
+                n_items = a.store_items if a.store_items is not None else 4 * B * world
+                if a.clips is not None:                         # clips: the feeder draws the frame too, and gathers only that frame
+                    from cavp_amd.clips import ClipFeeder, ClipFeedResult
+                    store = build_clip_store(stage, n_items, a.clips)
+                    feeder = ClipFeeder(store, batch=B, seed=1234, rank=rank, world=world)
+                    fed = ClipFeedResult(B, store, dev)
+                else:
+                    from cavp_amd.store import BatchFeeder, FeedResult
+                    store = build_store(stage, n_items)
+                    feeder = BatchFeeder(store, batch=B, seed=1234, rank=rank, world=world)
+                    fed = FeedResult(B, store, dev)
                 s_frames, s_masks, s_sizes = fed.frames, fed.masks, fed.sizes
         if a.raw_audio:
             from cavp_amd.wave import WaveResult, WaveStage
-            wave_stage = WaveStage(audio_len=hyp.audio_len, rates=(RAW_RATE,), max_sources=1, max_channels=2, max_len=RAW_LEN,
-                                   device=dev, max_batch=B)
+            segments = a.clips if a.clips is not None else 1     # clips: T seconds are cropped, the drawn frame's second is kept
+            wave_stage = WaveStage(audio_len=hyp.audio_len * segments, rates=(RAW_RATE,), max_sources=1, max_channels=2, max_len=RAW_LEN,
+                                   segments=segments, device=dev, max_batch=B)
+            wave_select = fed.select if segments > 1 else None
             s_pcm = torch.zeros((B, 1, 2, RAW_LEN), dtype=torch.int16, device=dev)
             s_pcm_len = torch.full((B, 1), RAW_LEN, dtype=torch.int32, device=dev)
             s_rate_idx = torch.zeros((B, 1), dtype=torch.int32, device=dev)
@@ -278,7 +330,7 @@ def main():
                     s_label.copy_(labelled.label)
                     s_img_label.copy_(labelled.img_label)
                 if wave_stage is not None:   # raw PCM -> the mono 16 kHz second the pair builder takes
-                    wave_stage(s_pcm, s_pcm_len, s_rate_idx, s_n_ch, out=cut)
+                    wave_stage(s_pcm, s_pcm_len, s_rate_idx, s_n_ch, select=wave_select, out=cut)
                 pairs(s_wave if wave_stage is None else cut.waveform, s_label, s_img_label, overwrite, out=built)
                 s_audio.copy_(front(built.waveforms))
                 s_shuf.copy_(built.label_shuffle)
@@ -309,7 +361,46 @@ def main():
             pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
             crit.manual_seed(1234 + rank)
 
+    validate = None
+    if a.validate_every is not None:
+        from cavp_amd.clips import ClipEvalResult
+        from cavp_amd.metrics import ClipValidation
+        T, Bv = a.clips, B // a.clips                           # Bv * T <= B frames per step: the stages' max_batch holds
+        val_feeder = ClipFeeder(store, batch=Bv, rank=rank, world=world)
+        ev = ClipEvalResult(Bv, store, dev)
+        cv = ClipValidation(num_classes=pairs.K, ignore_index=255, max_frames=Bv * T, device=dev)
+        # an augmentation stage of its own: eval_ draws nothing but advances the stage's call counter, and the training stream
+        # must not depend on whether a validation pass ran
+        val_aug = FrameAugment(crop=(a.hw, a.hw), jitter=None, device=dev, max_batch=Bv * T, stage=stage, resize=a.resize)
+        v_aug, v_lab = AugResult(Bv * T, (a.hw, a.hw), dev), LabelResult(Bv * T, pairs.K, (a.hw, a.hw), dev, True)
+        v_cut = WaveResult(Bv, 16000 * T, dev)
+
+        def validate():
+            """One pass over this rank's share of the store; every launch reads device values only"""
+            model.eval()
+            cv.reset()
+            for _ in range(val_feeder.steps_per_pass):
+                val_feeder.feed_clips(out=ev)
+                val_aug.eval_(ev.frames.view(Bv * T, *stage, 3), ev.masks.view(Bv * T, *stage), ev.sizes, out=v_aug)
+                stage_labels(v_aug.label, out=v_lab)
+                if T > 1:
+                    wave_stage(ev.pcm, ev.length, ev.rate_idx, ev.n_ch, out=v_cut)
+                    audio = front(v_cut.waveform.view(Bv * T, 1, 16000))
+                else:
+                    audio = front(wave_stage(ev.pcm, ev.length, ev.rate_idx, ev.n_ch).waveform)
+                cv.update(model.predict(v_aug.image, audio), v_lab.label.view(Bv, T, a.hw, a.hw), ev.count)
+            model.train()
+            val_aug.check()
+            cv.check()
+            return cv.results()
+
     for it in range(a.steps):
+        if validate is not None and it > 0 and it % a.validate_every == 0:
+            all_, ms = validate()
+            if rank == 0:
+                fmt = lambda r: "mIoU {:.4f} acc {:.4f} fdr {:.4f} f1 {:.4f} f0.3 {:.4f}".format(*(float(v) for v in r))
+                print(f"validation before step {it}: {val_feeder.steps_per_pass} steps of {Bv} clips x {T} frames;  ALL {fmt(all_)};  "
+                      f"MS {fmt(ms)}", flush=True)
         if a.fixed_batch:
             g = torch.Generator().manual_seed(1234 + rank)      # the same batch every step
         if feeder is not None:                                  # resident: the batch is drawn and gathered inside the graph
@@ -416,6 +507,10 @@ def main():
         feeder.check()
         print(f"resident: {len(store)} items, {store.nbytes / 1e6:.1f} MB on the device ({store.arena_bytes()}); step {feeder.step()} = epoch "
               f"{feeder.epoch_of(feeder.step())} of {feeder.steps_per_epoch} steps; items of the last batch {fed.index[:8].tolist()} ...")
+        if a.clips is not None:
+            print(f"clips: {a.clips} frames each, {store.total_frames} frames resident; frames drawn in the last batch "
+                  f"{fed.select[:8].tolist()} ..." + (f"; the validation feeder stands at step {val_feeder.eval_step()}, the training "
+                  f"feeder's eval counter at {feeder.eval_step()}" if validate is not None else ""))
     if rank == 0 and wave_stage is not None:
         wave_stage.check()
         print(f"raw audio: {RAW_LEN / RAW_RATE:.0f} s of {RAW_RATE} Hz int16 stereo per row -> [B, 1, 16000] by WaveStage; rms of the last batch "
