@@ -170,6 +170,7 @@ PROTOTYPES = {
     "cavp_smallcin_kxk_im2col": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_space_to_depth": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_row_scale_add": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
+    "cavp_drop_path_draw": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),   # DropPath masks on the device (added to ABI 16)
     # ---- validation metrics ----
     "cavp_seg_confusion_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp]),
     "cavp_mask_iou_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp]),

@@ -825,6 +825,23 @@ class CAVP(nn.Module):
         mode of the BatchNorm layers needs a fresh `enable_graphed_autograd()`."""
         self.__dict__["_graphed_autograd"] = [] if on else None
 
+    def use_device_drop_path(self, seed: Optional[int] = 0):
+        """Opt-in, PVT only: the backbone's DropPath masks are drawn on the device (cavp_amd/droppath.py) - one launch
+        per training forward from the device state {seed, offset}, inside the graph of a captured step, instead of one
+        torch.rand per branch from the default CPU generator before every replay.  Returns the DropPathSampler (manual_seed,
+        offset, rollback_ranges); `seed=None` removes it and restores the host draws.  Set it before capturing: a graph keeps the
+        way of drawing it was captured with.  Data-parallel runs pass a seed of their own per rank (the reference seeds
+        `seed + local_rank`)."""
+        if self.seg_model != "PVT":
+            raise CavpError("use_device_drop_path: only the PVT backbone has DropPath (seg_model is %r)" % (self.seg_model,))
+        if seed is None:
+            self.backbone.__dict__.pop("_dp_sampler", None)
+            return None
+        from .droppath import DropPathSampler
+        dp = DropPathSampler(seed)
+        self.backbone.__dict__["_dp_sampler"] = dp     # not a module attribute: it stays out of the state_dict
+        return dp
+
     def params_without_grad(self):
         """Parameters the forward never touches (present in checkpoints only): torch leaves their .grad None."""
         ps = [self.cross_att.pos_embed_v, self.cross_att.pos_embed_a]
@@ -963,6 +980,11 @@ class CAVP(nn.Module):
                 audio.copy_(front(built.waveforms)); shuf.copy_(built.label_shuffle)
         The warm-up passes run it for real: a PairBuilder's and the device sampler's call counters (and the sound bank) have
         advanced by three calls when this returns - reseed (`manual_seed`) after the capture, unless `rollback=` is given.
+        PVT with a device DropPath sampler (`use_device_drop_path`, set before this call): the forward's draw is one launch of
+        graph 1 and replay() draws nothing on the host.  The two warm-up passes draw for real and the captured pass only records
+        its launch, so the sampler's offset stands 2 above its value before the call when this returns (measured:
+        tests/test_gpu_droppath.py prints it); with `rollback=` and the sampler registered (`rb.add(dp)`) it is unchanged.  The
+        replay closure holds the sampler whose state the graph reads; a graph captured without one keeps the host refresh.
         rollback: a frozen cavp_amd.rollback.StepRollback; needs an optimiser whose StepGuard has a skip rule on.  Its save() is the
         first launch of each pass - before the prologue, hence before any side stream forks - and its restore_if_skipped(guard)
         follows the guarded update directly (in the graph, or behind the eager update when collectives are on): a replay whose
@@ -1077,10 +1099,13 @@ class CAVP(nn.Module):
             self.params_changed()
         if optimizer is not None and not static_losses:   # collectives on: the update was not issued during the capture
             static_losses.append(tuple(self._last_losses) if contrast is not None else (loss,))
+        # with a device sampler (use_device_drop_path) the captured draw is in graph 1: nothing to refresh on the host.  replay()
+        # holds the sampler, whose state and tables the graph reads, for as long as it lives
+        dp_sampler = getattr(self.backbone, "_dp_sampler", None) if self.seg_model == "PVT" else None
 
         def replay():
             self.params_changed()   # the graph updates the running statistics (and is usually followed by an optimiser step)
-            if self.seg_model == "PVT" and getattr(self, "_pvt_drop_scales", None) is None:
+            if self.seg_model == "PVT" and getattr(self, "_pvt_drop_scales", None) is None and dp_sampler is None:
                 from .pvt_train import refresh_drop_path
                 refresh_drop_path(self.backbone, image.shape[0], image.device)   # the graph reads the persistent mask buffer
             graphs[0].replay()

@@ -26,7 +26,7 @@ struct AugScales { int n; int num[kAugMaxScales]; };   // scale = num / 64
 struct AugNorm { float mean[3], std[3]; int fill[3]; };
 
 // ------------------------------------------------------------------------------------------------------------------- plan
-__device__ __forceinline__ float aug_u01(unsigned r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }   // [0, 1), 24 bits
+// (aug_u01 - a draw's top 24 bits as a float in [0, 1) - is in common.h, shared with pvt_train.hip's DropPath draw)
 __device__ __forceinline__ int aug_below(unsigned r, int n) { return (int)(((unsigned long long)r * (unsigned)n) >> 32); }   // [0, n)
 
 // PIL's NEAREST resize (ImagingScaleAffine): xo = a / 2, xo += a per output index, a = in / out in double; the source index is the

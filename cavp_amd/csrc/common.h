@@ -314,6 +314,9 @@ __device__ __forceinline__ unsigned long long philox_key(unsigned c0, unsigned c
   return ((unsigned long long)c0 << 32) | c1;
 }
 
+// a 32-bit draw as a float in [0, 1): its top 24 bits, exact (augment.hip's factors, pvt_train.hip's DropPath masks)
+__device__ __forceinline__ float aug_u01(unsigned r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
+
 // floor(n / d) for 0 <= n < 2^31 by a host-prepared multiplier: m = floor(2^(31+L) / d) + 1, L = ceil(log2 d), shift = 31 + L
 // (exact: the error term n * e / 2^(31+L), e <= 1, stays below 1/d because n < 2^31 <= 2^(31+L) / d).  The tile set-up did
 // two real integer divisions per operand row (~40 VALU each, 8 per thread and tile): ~1 us of every tile at 2 waves per SIMD.

@@ -680,6 +680,26 @@ __global__ __launch_bounds__(256) void row_scale_add_kernel(const T* __restrict_
   }
 }
 
+// The factors themselves, drawn on the device (cavp_drop_path_draw): out[k][b] = floor(keep[k] + u) / keep[k] with u the top 24
+// bits of the first word of Philox4x32-10 at counter = (sample b, branch row k, offset_lo, offset_hi), key = seed - the
+// convention of augment.hip's draw.  floor(keep + u) is 1 exactly when the f32 sum reaches 1 (0 < keep <= 1, 0 <= u < 1), and
+// inv_keep is the host's f32 1 / keep, so the result is timm's `rand.add_(keep).floor_().div_(keep)` bit for bit.  One workgroup;
+// every thread reads {seed, offset} before thread 0 moves the offset (as aug_plan_kernel does).
+__global__ __launch_bounds__(1024) void drop_path_draw_kernel(long long* __restrict__ state, const float* __restrict__ keep,
+                                                              const float* __restrict__ inv_keep, int n, int B,
+                                                              float* __restrict__ out) {
+  const unsigned long long seed = (unsigned long long)state[0], off = (unsigned long long)state[1];
+  const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), o0 = (unsigned)off, o1 = (unsigned)(off >> 32);
+  __syncthreads();
+  if (threadIdx.x == 0) state[1] = (long long)(off + 1ull);
+  const int total = n * B;   // <= 2^20 (checked by the host)
+  for (int i = threadIdx.x; i < total; i += 1024) {
+    const int k = i / B, b = i - k * B;
+    const float u = aug_u01((unsigned)(philox_key((unsigned)b, (unsigned)k, o0, o1, k0, k1) >> 32));
+    out[i] = keep[k] + u >= 1.0f ? inv_keep[k] : 0.0f;
+  }
+}
+
 // dkv[i] = sum_s slabs[s][i] (split order), 16-byte vectors; TO = float or bf16_t (the compute dtype of the consumer: the cast pass
 // that used to follow is folded in)
 template <typename TO>
@@ -846,5 +866,14 @@ extern "C" int cavp_row_scale_add(int32_t dtype, const void* x, const void* bran
   hipStream_t st = (hipStream_t)stream;
   cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
     row_scale_add_kernel<T><<<(int)nb, 256, 0, st>>>((const T*)x, (const T*)branch, sample_scale, (T*)out, psv, total); });
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_drop_path_draw(int64_t* state, const float* keep, const float* inv_keep, int32_t n, int32_t B, float* out,
+                                   void* stream) {
+  if (!state || !keep || !inv_keep || !out || n < 1 || B < 1) return CAVP_ERR_BAD_ARG;
+  if ((long long)n * B > (1ll << 20)) return CAVP_ERR_UNSUPPORTED;
+  if ((uintptr_t)state % 8) return CAVP_ERR_ALIGN;
+  drop_path_draw_kernel<<<1, 1024, 0, (hipStream_t)stream>>>((long long*)state, keep, inv_keep, n, B, out);
   CHECK_LAUNCH();
 }

@@ -167,7 +167,10 @@ def draw_drop_path_scales(bb, B: int, device, _refresh_only: bool = False) -> Li
     the block's probability is 0 or the backbone is in eval mode.  Drawn like timm 0.4.9's drop_path - `floor(keep +
     torch.rand((B, 1, 1)))`, one draw per branch from the default CPU generator - then moved in ONE copy into a persistent
     device buffer (`bb._dp_buf`); an eager pass works on a private clone of it.  While a hipGraph is being captured nothing is drawn: the graph reads that buffer, and
-    `CAVP.capture_train_step`'s replay() refreshes it before every launch (refresh_drop_path)."""
+    `CAVP.capture_train_step`'s replay() refreshes it before every launch (refresh_drop_path).
+    With a device sampler (`CAVP.use_device_drop_path`, cavp_amd/droppath.py) nothing is drawn on the host: one launch of
+    cavp_drop_path_draw on the current stream writes all rows - into `bb._dp_buf` during a capture, so every replay draws fresh
+    masks in the graph, and into a fresh private table in an eager pass."""
     probs = [blk.drop_prob for i in range(4) for blk in getattr(bb, f"block{i + 1}") for _ in range(2)]
     if not bb.training or not any(probs):
         return [None] * len(probs)
@@ -177,7 +180,14 @@ def draw_drop_path_scales(bb, B: int, device, _refresh_only: bool = False) -> Li
     if buf is None or tuple(buf.shape) != (n, B) or buf.device != dev:
         buf = torch.ones((n, B), dtype=torch.float32, device=dev)
         bb.__dict__["_dp_buf"] = buf          # not a registered buffer: it must stay out of the state_dict
-    if not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+    sampler = None if _refresh_only else getattr(bb, "_dp_sampler", None)
+    if sampler is not None:
+        if dev.type != "cuda":
+            raise CavpError("the device DropPath sampler draws on a HIP device (use_device_drop_path(None) restores the host draws)")
+        capturing = torch.cuda.is_current_stream_capturing()
+        use = sampler.draw([p for p in probs if p > 0], B,
+                           buf if capturing else torch.empty((n, B), dtype=torch.float32, device=buf.device))
+    elif not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
         # one torch.rand((B, 1, 1)) per branch, in forward order (the reference's draws); the arithmetic on all rows at once
         keeps = torch.tensor([1.0 - p for p in probs if p > 0], dtype=torch.float32).view(n, 1)
         rows = torch.stack([torch.rand((B, 1, 1), dtype=torch.float32).view(B) for p in probs if p > 0])
@@ -216,7 +226,9 @@ def draw_drop_path_scales(bb, B: int, device, _refresh_only: bool = False) -> Li
 
 
 def refresh_drop_path(bb, B: int, device) -> None:
-    """New DropPath masks for the next replay of a captured training step."""
+    """New DropPath masks for the next replay of a captured training step, always drawn on the host: a graph captured without a
+    device sampler goes on reading host-drawn masks whatever is set later, and one captured with a sampler draws its own - its
+    replay() does not call this."""
     draw_drop_path_scales(bb, B, device, _refresh_only=True)
 
 

@@ -10,6 +10,7 @@ holds a device-resident table of those byte ranges and a shadow arena of the sam
     rb.add(pairs)              # PairBuilder: bank, ring heads, {seed, offset}      (bank=False leaves the bank out)
     rb.add(augment)            # FrameAugment: {seed, offset}
     rb.add(crit)               # ContrastLoss device sampler: {seed, offset}
+    rb.add(dp)                 # DropPathSampler (PVT, model.use_device_drop_path): {seed, offset}
     rb.add_tensor(t)           # anything else
     rb.freeze()                # the table and the shadow arena (one allocation); no add*() after it
     replay = model.capture_train_step(..., optimizer=opt, prologue=prologue, rollback=rb)
@@ -158,7 +159,7 @@ class StepRollback:
 
     def add(self, stage, **kw) -> "StepRollback":
         """A stage that names its own state through `rollback_ranges()`: PairBuilder (`bank=False` leaves the sound bank out),
-        FrameAugment, ContrastLoss with the device sampler."""
+        FrameAugment, ContrastLoss with the device sampler, the feeders, PVT's DropPathSampler."""
         fn = getattr(stage, "rollback_ranges", None)
         if fn is None:
             raise _lib.CavpError(f"StepRollback.add: {type(stage).__name__} has no rollback_ranges(); use add_tensor")

@@ -1604,6 +1604,8 @@ class GraphedTrainStep:
         self.d_pred = torch.zeros((B2, C) + tuple(image.shape[-2:]), dtype=torch.float32, device=dev)
         self.d_fusion = None      # allocated by the first forward (needs the fusion map's size)
         self._state = None
+        # a device DropPath sampler (CAVP.use_device_drop_path): graph A draws the masks itself and reads the sampler's state
+        self.dp_sampler = getattr(model.backbone, "_dp_sampler", None) if model.seg_model == "PVT" else None
         # the warm-up passes below run the real kernels: BatchNorm running statistics / counters are put back afterwards
         saved = [(b, b.detach().clone()) for b in model.buffers()]
         with torch.no_grad():
@@ -1684,7 +1686,7 @@ class GraphedTrainFunction(torch.autograd.Function):
         step.release_adopted(params)      # (graph A starts by clearing the arena)
         step.image.copy_(image)
         step.audio.copy_(audio)
-        if m.seg_model == "PVT" and getattr(m, "_pvt_drop_scales", None) is None:
+        if m.seg_model == "PVT" and getattr(m, "_pvt_drop_scales", None) is None and step.dp_sampler is None:
             from .pvt_train import refresh_drop_path
             refresh_drop_path(m.backbone, image.shape[0], image.device)   # the graph reads the persistent mask buffer
         step.gA.replay()

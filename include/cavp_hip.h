@@ -699,6 +699,14 @@ int cavp_space_to_depth(int32_t dtype, const void* src, void* dst, int32_t B, in
  * gradient sample_scale[b] * g.  per_sample = elements per batch item. */
 int cavp_row_scale_add(int32_t dtype, const void* x, const void* branch, const float* sample_scale, void* out, int32_t B,
                        int64_t per_sample, void* stream);
+/* DropPath factors drawn on the device (one entry point added to ABI 16; nothing else changed; opt-in, cavp_amd/droppath.py).
+ * state: int64 {seed, offset} on the device, the 16-byte head of the frame augmentation's state block.  keep, inv_keep: f32 [n],
+ * 1 - p and the f32 quotient 1 / keep of every branch with p > 0, in forward order.  out: f32 [n][B], dense.
+ *   r = Philox4x32-10(counter = (b, k, offset_lo, offset_hi), key = (seed_lo, seed_hi));  u = (r[0] >> 8) * 2^-24
+ *   out[k][b] = keep[k] + u >= 1 ? inv_keep[k] : 0      (the sum in f32: timm 0.4.9's floor(keep + rand) / keep)
+ * then offset += 1.  One workgroup, plain stores, no host synchronisation: capturable.  n >= 1, B >= 1 and non-null pointers
+ * (CAVP_ERR_BAD_ARG), n * B <= 2^20 (CAVP_ERR_UNSUPPORTED). */
+int cavp_drop_path_draw(int64_t* state, const float* keep, const float* inv_keep, int32_t n, int32_t B, float* out, void* stream);
 
 /* ---- validation metrics (ABI 13; utils/eval_utils.py MIoU / ForegroundDetect, utils/avsbench_utils.py mask_iou / Eval_Fmeasure) ----
  * Integer counts only, accumulated with integer atomics: results are independent of arrival order.  The float finalisation stays

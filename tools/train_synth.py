@@ -14,6 +14,7 @@ usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] 
                                    [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]
                                    [--resident [--store-items N] [--clips T [--validate-every K]]]]
                                    [--guard [--max-norm X] [--rollback]]] [--preview DIR]
+                                   [--seg-model DeepLabV3Plus|PVT [--device-droppath]]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
 ContrastLoss with the device sampler on the fusion map; the shuffle labels are the labels with the second half of the batch set to 0.
@@ -57,6 +58,10 @@ returns the records written since (step, rate, both losses, gradient norm, coeff
 their own warm-up passes, so nothing is reloaded or reseeded behind them.  At the end the rollback's restore count is printed next to
 the guard's skipped count; the run fails if the two differ.
 
+--device-droppath (with --seg-model PVT; an error otherwise): the backbone's DropPath masks are drawn on the device
+(model.use_device_drop_path(seed=1234 + rank), cavp_amd/droppath.py) - one launch per forward, inside the graph with --graph, where
+the host no longer draws or uploads anything before a replay; with --rollback the sampler's {seed, offset} joins the rollback.
+
 --preview DIR: after training, the reference trainers' image upload (Tensorboard.upload_wandb_image) without its whole-tensor host
 copies: eval mode, model.predict on the last batch, cavp_amd.preview.PreviewStage on image, label and mask, one 5-byte-per-pixel copy,
 and the x / y / y_tilde pictures of the first frames written to DIR as PNG files (needs PIL).
@@ -87,6 +92,8 @@ def main():
     ap.add_argument("--weight-decay", type=float, default=1e-4)
     ap.add_argument("--total-iters", type=int, default=1000)
     ap.add_argument("--seg-model", choices=["DeepLabV3Plus", "PVT"], default="DeepLabV3Plus", help="PVT = config #4's PVTv2-B5 backbone")
+    ap.add_argument("--device-droppath", action="store_true", help="with --seg-model PVT: draw the DropPath masks on the device "
+                    "(one launch per forward, in the graph with --graph) instead of on the host before every step")
     ap.add_argument("--fixed-batch", action="store_true", help="train on ONE batch (over-fit sanity: the loss must fall)")
     ap.add_argument("--from-waveform", action="store_true", help="start from 16 kHz waveforms (HIP log-mel front-end)")
     ap.add_argument("--contrast", action="store_true", help="add the pixel-level contrastive term to the native step (device sampler)")
@@ -136,6 +143,8 @@ def main():
         ap.error("--rollback needs --guard: the guard's skip word decides the restore")
     if a.graph and not a.pairs:
         ap.error("--graph needs --from-waveform --contrast --pairs")
+    if a.device_droppath and a.seg_model != "PVT":
+        ap.error("--device-droppath needs --seg-model PVT: only the PVT backbone has DropPath")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -159,6 +168,7 @@ def main():
     model = CAVP(50, None, num_classes=a.num_classes, args=hyp)
     model.load_state_dict(synth_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}, seed=1))
     model.train().to(dev).set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    drop_path = model.use_device_drop_path(seed=1234 + rank) if a.device_droppath else None   # each rank its own stream of masks
     sched = warmup_poly_lr(a.lr, a.lr_power, a.total_iters, 0)
     front = MelFrontEnd(hyp, device=dev) if a.from_waveform else None
     crit = None
@@ -342,6 +352,8 @@ def main():
                 rb.add(aug)
             if feeder is not None:
                 rb.add(feeder)                                  # a skipped step sees the same batch again
+            if drop_path is not None:
+                rb.add(drop_path)                               # ... and the same DropPath masks
             rb.freeze()
         replays = []
         for ow in (False, True):
@@ -357,6 +369,8 @@ def main():
                 aug.manual_seed(1234 + rank)
             if feeder is not None:
                 feeder.set_step(0)
+            if drop_path is not None:
+                drop_path.manual_seed(1234 + rank)
             pairs.manual_seed(1234 + rank)
             pairs.load_bank(torch.zeros(pairs.K, pairs.S, pairs.A, device=dev))
             crit.manual_seed(1234 + rank)
