@@ -202,6 +202,9 @@ PROTOTYPES = {
     "cavp_videoval_frame_stats": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp,
                                          _vp, _vp]),
     "cavp_videoval_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # ---- semantic validation: per-frame, per-class IoU / F-score of the AVSBench-semantic metric (added to ABI 16) ----
+    "cavp_semval_frame_counts": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "cavp_semval_combine": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     # ---- wave stage: resample, crop and mix raw audio clips (added to ABI 16) ----
     "cavp_wave_tile": (_i32, []),
     "cavp_wave_stage": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32,

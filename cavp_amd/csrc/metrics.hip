@@ -19,7 +19,9 @@
 //                  histogram and the seg_confusion counts in scratch, then a flag per frame from its histogram and the adds.
 //   videoval:      the frames of a batch of videos in one pass: per frame the mask_iou_stats sums and the fmeasure_hist histograms
 //                  in scratch, the seg_confusion counts into the global matrix; then one workgroup per video finishes J and F in
-//                  float32 (the one float tail that runs on the device: per-video scores are stored results).
+//                  float32 (a float tail that runs on the device: per-video scores are stored results).
+//   semval:        the per-frame, per-class IoU / F-score of utils/avsbench_metrics.py: per frame the three class-area vectors and the
+//                  binary-IoU sums in scratch, then one thread per class adds the frames' float32 scores in ascending order.
 #include "common.h"
 #include "host_util.h"
 
@@ -847,6 +849,223 @@ __global__ __launch_bounds__(kThreads) void videoval_combine_kernel(unsigned lon
   }
 }
 
+// ---- semantic validation: per-frame, per-class IoU and F-score of the AVSBench-semantic metric (utils/avsbench_metrics.py) -------
+// frame_kernel:   per participating frame, from one read of the prediction, the three class-area vectors inter | pred | lab and the
+//                 four binary-IoU sums as u32 in per-frame scratch [3K + 4].
+// combine_kernel: one thread per class walks the call's frames in ascending order (float32, one IEEE operation at a time) and adds
+//                 the call's partial to the running accumulators; the last workgroup to finish turns the per-frame IoUs the class
+//                 threads left in the scratch into frame_miou, finishes the binary IoU and leaves the scratch zero.
+enum { kSvBadMask = 0, kSvBadCount = 1, kSvFrames = 2, kSvTicket = 3 };   // state words
+constexpr int kSemvalQuads = 2;    // quads per thread of a frame workgroup
+constexpr int kSemvalChunk = 16;   // frames a class thread loads side by side
+constexpr int kSemvalCombineThreads = 1024;   // 16 waves: the last workgroup takes 16 frames at a time
+constexpr int kSemvalCombineWaves = kSemvalCombineThreads / 64;
+
+// grid (chunks, B*T): a workgroup belongs to one frame.  One thread = 4 consecutive pixels; block-uniform trip count (add_bins
+// ballots).  LDS: [K] inter, [K] pred, [K] lab, [4] binary sums.  Every index is guarded before use: a prediction by p < K (logits
+// have C == K channels, a mask byte >= K sets no class bin), a label by 0 <= v < K.
+template <bool kMask, bool kVec>
+__global__ __launch_bounds__(kThreads) void semval_frame_kernel(const void* __restrict__ pred, const long long* __restrict__ labels,
+                                                               const void* __restrict__ count, int count_i64, int T, long long HW,
+                                                               int K, unsigned* __restrict__ scratch,
+                                                               unsigned long long* __restrict__ state) {
+  extern __shared__ unsigned lds[];
+  const int n = blockIdx.y, b = n / T, t = n - b * T;
+  if (t >= clip_count(count, count_i64, b, T)) return;   // workgroup-uniform: the frame is not read
+  const int words = 3 * K + 4;
+  lds_counts_clear(lds, words);
+  const long long* lab_n = labels + (long long)n * HW;
+  const long long nq = (HW + 3) >> 2;
+  unsigned bad_mask = 0;
+  int bin[4] = {0, 0, 0, 0};   // #(P and G), #(P or G), #(neither), #G with P = (p != 0), G = (v != 0)
+  for (long long base = (long long)blockIdx.x * kThreads; base < nq; base += (long long)gridDim.x * kThreads) {
+    const long long q = base + threadIdx.x;
+    int bi[4] = {-1, -1, -1, -1}, bp[4] = {-1, -1, -1, -1}, bl[4] = {-1, -1, -1, -1};
+    if (q < nq) {
+      const long long p0 = q * 4;
+      const int np = quad_pixels<kVec>(HW - p0);
+      long long tv[4];
+      load_quad<long long, kVec>(lab_n + p0, np, tv);
+      int p[4];
+      if (kMask) {
+        unsigned char m[4];
+        load_quad<unsigned char, kVec>((const unsigned char*)pred + (long long)n * HW + p0, np, m);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = m[j];
+      } else {
+        quad_argmax_nchw<kVec>((const float*)pred + (long long)n * K * HW + p0, K, HW, np, p);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j >= np) continue;
+        const long long v = tv[j];
+        const bool P = p[j] != 0, G = v != 0;
+        bin[0] += P && G;
+        bin[1] += P || G;
+        bin[2] += !P && !G;
+        bin[3] += G;
+        if (kMask && p[j] >= K) { ++bad_mask; continue; }
+        if (v < 0) continue;            // counts in none of the three areas
+        bp[j] = K + p[j];               // a label >= K (the ignore value) still counts the prediction: histc drops only the label
+        if (v < K) {
+          bl[j] = 2 * K + (int)v;
+          if (v == p[j]) bi[j] = p[j];
+        }
+      }
+    }
+    add_bins<true>(bi, lds, (unsigned*)nullptr);
+    add_bins<true>(bp, lds, (unsigned*)nullptr);
+    add_bins<true>(bl, lds, (unsigned*)nullptr);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int v = bin[k];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(lds + 3 * K + k, (unsigned)v);
+  }
+  if (bad_mask) atomicAdd(state + kSvBadMask, (unsigned long long)bad_mask);
+  lds_counts_flush(lds, words, scratch + (size_t)n * words);   // its barrier covers the binary sums
+}
+
+// a word another workgroup of this launch has written: read at the device's level of coherence, never from this CU's cache
+__device__ __forceinline__ unsigned load_device_scope(const unsigned* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid ceil(K / 1024): one thread = one class.  acc: f32 [3K + 1] ious | fscores | cls_count | binary sum (running); last: f32
+// [3K + 1 + 2 * max_frames] the same of this call, then frame_miou and the frames' binary IoU.  Every float step is one IEEE
+// operation (__f*_rn: the build contracts a * b + c).
+__global__ __launch_bounds__(kSemvalCombineThreads) void semval_combine_kernel(unsigned* __restrict__ scratch, const void* __restrict__ count,
+                                                                 int count_i64, int B, int T, long long HW, int K, int max_frames,
+                                                                 float* __restrict__ acc, float* __restrict__ last,
+                                                                 unsigned long long* __restrict__ state) {
+  __shared__ int is_last;
+  __shared__ float biou[kSemvalCombineThreads];
+  const int N = B * T, words = 3 * K + 4;
+  const int c = blockIdx.x * kSemvalCombineThreads + threadIdx.x;
+  if (c < K) {
+    float s_iou = 0.f, s_f = 0.f, s_hit = 0.f;
+    for (int n0 = 0; n0 < N; n0 += kSemvalChunk) {
+      unsigned a[kSemvalChunk][3];
+      bool on[kSemvalChunk];
+#pragma unroll
+      for (int k = 0; k < kSemvalChunk; ++k) {
+        const int n = n0 + k, b = n / T;
+        on[k] = n < N && n - b * T < clip_count(count, count_i64, b, T);
+        if (on[k]) {
+          const unsigned* s = scratch + (size_t)n * words + c;
+          a[k][0] = s[0]; a[k][1] = s[K]; a[k][2] = s[2 * K];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kSemvalChunk; ++k) {   // ascending frames
+        if (!on[k]) continue;
+        const float inter = (float)a[k][0], pred = (float)a[k][1], lab = (float)a[k][2];
+        const float uni = __fsub_rn(__fadd_rn(pred, lab), inter);
+        const float iou = __fdiv_rn(inter, __fadd_rn(2.220446049250313e-16f, uni));
+        const float prec = __fdiv_rn(inter, pred), recall = __fdiv_rn(inter, lab);
+        float f = __fdiv_rn(__fmul_rn(__fmul_rn(1.3f, prec), recall), __fadd_rn(__fmul_rn(0.3f, prec), recall));
+        if (f != f) f = 0.f;
+        s_iou = __fadd_rn(s_iou, iou);
+        s_f = __fadd_rn(s_f, f);
+        if (uni != 0.f) s_hit = __fadd_rn(s_hit, 1.f);
+        unsigned* s = scratch + (size_t)(n0 + k) * words + c;
+        if (a[k][0]) s[0] = __float_as_uint(iou);   // the frame's IoU (non-zero iff inter is), for the last workgroup
+        if (a[k][1]) s[K] = 0u;
+        if (a[k][2]) s[2 * K] = 0u;
+      }
+    }
+    last[c] = s_iou;
+    last[K + c] = s_f;
+    last[2 * K + c] = s_hit;
+    acc[c] = __fadd_rn(acc[c], s_iou);
+    acc[K + c] = __fadd_rn(acc[K + c], s_f);
+    acc[2 * K + c] = __fadd_rn(acc[2 * K + c], s_hit);
+  }
+  if (gridDim.x == 1) {   // K <= 1024: this workgroup wrote every IoU itself, a barrier orders them; no ticket, no device-wide fence
+    __syncthreads();
+  } else {
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) is_last = atomicAdd(state + kSvTicket, 1ull) == (unsigned long long)(gridDim.x - 1);
+    __syncthreads();
+    if (!is_last) return;   // workgroup-uniform
+    __threadfence();        // every class thread of the launch has left its IoUs in the scratch
+    if (threadIdx.x == 0) atomicExch(state + kSvTicket, 0ull);
+  }
+
+  float* frame_miou = last + 3 * K + 1;
+  float* frame_biou = frame_miou + max_frames;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // frame_miou: one wave per frame; a lane loads its class, the wave adds the classes in ascending order (every lane the same sum)
+  for (int n = wave; n < N; n += kSemvalCombineWaves) {
+    const int b = n / T;
+    if (n - b * T >= clip_count(count, count_i64, b, T)) {   // wave-uniform
+      if (lane == 0) frame_miou[n] = -1.f;
+      continue;
+    }
+    unsigned* s = scratch + (size_t)n * words;
+    float sum = 0.f;
+    int nz = 0;
+    // the first two loads are in flight together (K <= 128 needs no more); a lane beyond K holds 0, which changes neither result
+    unsigned ahead = 64 + lane < K ? load_device_scope(s + 64 + lane) : 0u;
+    for (int c0 = 0; c0 < K; c0 += 64) {
+      const unsigned mine = c0 == 64 ? ahead : (c0 + lane < K ? load_device_scope(s + c0 + lane) : 0u);
+      if (mine) s[c0 + lane] = 0u;
+#pragma unroll
+      for (int i = 0; i < 64; ++i) {   // lane i's value through a scalar register: no LDS traffic
+        const float v = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)mine, i));
+        sum = __fadd_rn(sum, v);
+        nz += v != 0.f;
+      }
+    }
+    if (lane == 0) frame_miou[n] = __fdiv_rn(sum, (float)nz);   // no class with a non-zero IoU: 0 / 0, the reference's NaN
+  }
+  // binary IoU: the frames' quotients side by side, then added by one thread in ascending order
+  float bsum = 0.f;
+  int frames = 0;
+  for (int n0 = 0; n0 < N; n0 += kSemvalCombineThreads) {
+    const int n = n0 + threadIdx.x;
+    float v = -1.f;   // takes no part (a quotient is >= 0)
+    if (n < N) {
+      const int b = n / T;
+      if (n - b * T < clip_count(count, count_i64, b, T)) {
+        unsigned* s = scratch + (size_t)n * words + 3 * K;
+        unsigned inter = s[0], uni = s[1];
+        if (s[3] == 0u) { inter = s[2]; uni = (unsigned)HW; }   // an empty target: the background overlap over all pixels
+        v = __fdiv_rn((float)inter, __fadd_rn((float)uni, 1e-7f));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (s[k]) s[k] = 0u;
+        }
+      }
+      frame_biou[n] = v;
+    }
+    biou[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = N - n0 < kSemvalCombineThreads ? N - n0 : kSemvalCombineThreads;
+      for (int k = 0; k < m; ++k) {
+        if (biou[k] >= 0.f) { bsum = __fadd_rn(bsum, biou[k]); ++frames; }
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    last[3 * K] = bsum;
+    acc[3 * K] = __fadd_rn(acc[3 * K], bsum);
+    if (frames) atomicAdd(state + kSvFrames, (unsigned long long)frames);
+  }
+  if (count) {
+    unsigned bad = 0;
+    for (int b = threadIdx.x; b < B; b += kSemvalCombineThreads) {
+      const long long cb = clip_count_raw(count, count_i64, b);
+      bad += cb < 0 || cb > T;
+    }
+    if (bad) atomicAdd(state + kSvBadCount, (unsigned long long)bad);
+  }
+}
+
 // ---- host side: the checks the entry points share, run-time arguments -> template arguments -------------------------------------
 bool label_ok(int code) { return code == CAVP_I64 || code == CAVP_F32; }
 bool classes_ok(int K, int C) { return K >= C && K <= CAVP_METRICS_MAX_CLASSES; }
@@ -1048,5 +1267,42 @@ extern "C" int cavp_videoval_combine(int64_t* stats, uint32_t* hist, const void*
   const size_t shm = videoval_combine_words(pr_num) * sizeof(unsigned);
   videoval_combine_kernel<<<B, kThreads, shm, (hipStream_t)stream>>>((unsigned long long*)stats, hist, count, count_i64, B, T, HW, pr_num,
                                                                       max_videos, J, F, (unsigned long long*)state);
+  CHECK_LAUNCH();
+}
+
+static bool semval_shape_ok(int B, int T, int64_t HW, int K) {
+  return (long long)B * T <= 65535 && HW <= 0x7fffffffLL && K >= 2 && K <= CAVP_METRICS_MAX_CLASSES;   // grid.y; u32 counts; histc
+}
+
+extern "C" int cavp_semval_frame_counts(const void* pred, int32_t pred_is_mask, const int64_t* labels, const void* count,
+                                        int32_t count_i64, int32_t B, int32_t T, int32_t C, int64_t HW, int32_t K, uint32_t* scratch,
+                                        int64_t* state, void* stream) {
+  if (!pred || !labels || !scratch || !state || B <= 0 || T <= 0 || HW <= 0 || K <= 0) return CAVP_ERR_BAD_ARG;
+  if (!pred_is_mask && C != K) return CAVP_ERR_BAD_ARG;   // the metric takes its class number from the logits
+  if (!semval_shape_ok(B, T, HW, K)) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)labels & 7) || ((uintptr_t)scratch & 3) || ((uintptr_t)state & 7) || (!pred_is_mask && ((uintptr_t)pred & 3)) ||
+      !aligned_for(count, count_i64 != 0))
+    return CAVP_ERR_ALIGN;
+  const bool vec = (HW & 3) == 0 && al16(labels) && (pred_is_mask ? ((uintptr_t)pred & 3) == 0 : al16(pred));
+  // 2 quads per thread, as clipval_frame_kernel: 25 workgroups per frame at 224^2, each clears and flushes 3K + 4 counters
+  const dim3 grid(chunks_for((HW + 3) >> 2, kSemvalQuads * kThreads, 1 << 20), B * T);
+  const size_t shm = (size_t)(3 * K + 4) * sizeof(unsigned);   // at most 48 KiB + 16 bytes: always in LDS
+  hipStream_t s = (hipStream_t)stream;
+  cavp_dispatch_bool(pred_is_mask != 0, [&](auto m) { cavp_dispatch_bool(vec, [&](auto v) {
+    semval_frame_kernel<decltype(m)::value, decltype(v)::value><<<grid, kThreads, shm, s>>>(
+        pred, (const long long*)labels, count, count_i64, T, HW, K, scratch, (unsigned long long*)state); }); });
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_semval_combine(uint32_t* scratch, const void* count, int32_t count_i64, int32_t B, int32_t T, int64_t HW, int32_t K,
+                                   int32_t max_frames, float* acc, float* last, int64_t* state, void* stream) {
+  if (!scratch || !acc || !last || !state || B <= 0 || T <= 0 || HW <= 0 || K <= 0 || max_frames <= 0) return CAVP_ERR_BAD_ARG;
+  if ((long long)B * T > max_frames) return CAVP_ERR_BAD_ARG;
+  if (!semval_shape_ok(B, T, HW, K)) return CAVP_ERR_UNSUPPORTED;
+  if (((uintptr_t)scratch & 3) || ((uintptr_t)acc & 3) || ((uintptr_t)last & 3) || ((uintptr_t)state & 7) ||
+      !aligned_for(count, count_i64 != 0))
+    return CAVP_ERR_ALIGN;
+  semval_combine_kernel<<<(K + kSemvalCombineThreads - 1) / kSemvalCombineThreads, kSemvalCombineThreads, 0, (hipStream_t)stream>>>(
+      scratch, count, count_i64, B, T, HW, K, max_frames, acc, last, (unsigned long long*)state);
   CHECK_LAUNCH();
 }

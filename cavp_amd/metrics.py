@@ -23,7 +23,9 @@ forward), `reset()`, `counts()` (the device-side (K+1) x K confusion counts) and
 device tensor, without `.item()`), and `ClipValidation`: the validation loop of the AVSS trainers (trainer_cavp_avss_image.py:295-349)
 for whole batches of clips - every frame counted into an ALL matrix and, when its own label histogram says "multi-source", into an
 MS matrix as well, decided on the device; and `VideoValidation`: the validation loop of the AVSBench object trainer
-(trainer_cavp_avs_obj.py:292-363) - per-video J (mask_iou) and F (Eval_Fmeasure) of whole batches of videos, finished on the device."""
+(trainer_cavp_avs_obj.py:292-363) - per-video J (mask_iou) and F (Eval_Fmeasure) of whole batches of videos, finished on the device;
+and `SemanticValidation`: the AVSBench-semantic metric (utils/avsbench_metrics.py) - per-frame, per-class IoU and F-score of whole
+batches of clips, with `calc_color_miou_fscore` / `calc_color_miou` / `calc_binary_miou` under the reference's names."""
 from __future__ import annotations
 
 import numpy
@@ -35,7 +37,7 @@ from .train_ops import zero_ as _zero_
 from .train_ops import zeros as _zeros
 
 __all__ = ["MIoU", "ForegroundDetect", "get_performance", "mask_iou", "Eval_Fmeasure", "fmeasure_curve", "ClipValidation",
-           "VideoValidation"]
+           "VideoValidation", "SemanticValidation", "calc_color_miou_fscore", "calc_color_miou", "calc_binary_miou"]
 
 
 def get_performance(miou_measure_in, fg_measure_in, class_list=None):
@@ -700,3 +702,276 @@ class VideoValidation:
             raise CavpError(f"VideoValidation: {bad[0]} label(s) outside {{0, 1, {self.ignore_index}}}, {bad[1]} mask value(s) >= "
                             f"{self.num_classes}, {bad[2]} count(s) outside [0, T], {bad[3]} video(s) beyond max_videos = "
                             f"{self.max_videos} since the last check")
+
+
+class SemanticValidation:
+    """The AVSBench-semantic metric (utils/avsbench_metrics.py: calc_color_miou_fscore, calc_color_miou, calc_binary_miou; the
+    reference's README calls it "Instance-level Evaluation") for whole batches of clips, without the host:
+
+        sv = SemanticValidation(num_classes=K, max_frames=320, device="cuda:0")
+        sv.update(model.predict(image, audio), labels, count)            # or sv.update_lowres(model.predict_lowres(...), ...)
+        r = sv.results()                                                 # r["miou"], r["fscore"], r["jf"], r["binary_miou"], ...
+
+    pred: dense float32 logits [B*T, K, H, W] (exactly K channels; argmax: first maximal index, a NaN is the maximum; the
+    reference's softmax in front of the argmax does not change it and is not computed), or the dense uint8 class mask [B*T, H, W] of
+    CAVP.predict.  labels: dense int64 [B, T, H, W] (or [N, H, W] with count=None); never written.  count: device int32 / int64 [B],
+    the reference's mask_num per clip: frame t of clip b takes part iff t < clamp(count[b], 0, T) (None: every frame); a frame that
+    takes no part is not read.
+
+    Per participating frame, three integer vectors over the classes: inter[c] = #(p == c and l == c), pred[c] = #(p == c and l >= 0),
+    lab[c] = #(l == c) - the reference's three torch.histc(bins=K, min=1, max=K) areas.  A pixel with l < 0 counts nowhere; a pixel
+    with l >= K (the ignore value 255 included) counts in pred only: the reference's histc drops the label and keeps the
+    prediction, and that quirk is kept.  From them in float32, one IEEE operation at a time, in the reference's grouping: iou =
+    inter / (2.22e-16 + union), f = 1.3 precision recall / (0.3 precision + recall) (NaN -> 0), hit = (union != 0), and the frame's
+    mean IoU over the classes with a non-zero IoU (NaN when there is none, as in the reference).  Within one update the per-class
+    sums of iou, f and hit start from zero and take the frames in ascending (b, t): exactly what one call of calc_color_miou_fscore
+    returns (last_call()).  The call's sums are then added to the running float32 accumulators, as the benchmark driver's
+    `miou_pc += _miou_pc` does (accumulators()).  The binary IoU of calc_binary_miou (foreground = class != 0, over all pixels; an
+    empty target scores its background overlap) accumulates the same way.
+
+    results() = the published benchmark driver's reduction: miou_pc = ious / cls_count and fscore_pc = fscores / cls_count (NaN ->
+    0), their means over all K classes, jf = (miou + fscore) / 2, binary_miou = binary_sum / frames, in float32 torch operations
+    from ONE host copy.  That driver is not part of the reference tree, so this last step is pinned by the restatement
+    tests/_semval_ref.py only; everything up to the accumulators is held to the reference's own functions by
+    tests/golden/semval.npz.  The label-vocabulary remapping of the benchmark's v1s / v1m / v2 subsets is the caller's.
+
+    update() is two launches and update_lowres() three (csrc/metrics.hip); neither synchronises, neither allocates
+    after its first call, so both can be captured in a hipGraph with CAVP.predict / predict_lowres (run one eager call first).  The
+    counts are integer adds and the float tail runs in a fixed order, one thread per class: the results do not depend on arrival
+    order.  A mask byte >= K sets no class counter, a count[b] outside [0, T] is clamped; each is counted on the device, and check()
+    raises if there were any.  The accumulators are per process: summing them across ranks is the caller's job (float32 adds, in a
+    rank order of the caller's choice)."""
+
+    def __init__(self, num_classes: int, max_frames: int = 320, device=None):
+        k = int(num_classes)
+        if not 2 <= k <= MAX_CLASSES:
+            raise CavpError(f"SemanticValidation: 2 <= num_classes <= {MAX_CLASSES}, got {num_classes} (one class is degenerate in "
+                            f"the reference's histc)")
+        if not 1 <= int(max_frames) <= MAX_CLIP_FRAMES:
+            raise CavpError(f"SemanticValidation: 1 <= max_frames <= {MAX_CLIP_FRAMES}")
+        self.num_classes, self.max_frames = k, int(max_frames)
+        self.words = 3 * k + 4
+        self.scratch_bytes = self.max_frames * self.words * 4   # at most 3.2 GB (K = 4096, 65535 frames); 72 KB at K = 71, 80 frames
+        self._device = device
+        self._res = None             # device buffers, allocated by the first update (the constructor touches no device)
+        self._lowres = {}            # (N, H, W) -> mask of update_lowres
+        self._last_frames = 0
+
+    # ---- device state ------------------------------------------------------------------------------------------------------
+    def _bind(self, res, scratch, last):
+        """Take the device buffers.  res int64 [4 + ceil((3K + 1) / 2)]: the state words and the float32 accumulators ious | fscores
+        | cls_count | binary_sum side by side, so that results() is one host read; scratch int32 [max_frames, 3K + 4] (zero at
+        rest); last float32 [3K + 1 + 2 * max_frames]: the last call's sums, frame_miou and the frames' binary IoU."""
+        k, mf = self.num_classes, self.max_frames
+        sw = ops.SEMVAL_STATE_WORDS
+        want = ((res, torch.int64, sw + (3 * k + 2) // 2), (scratch, torch.int32, mf * self.words),
+                (last, torch.float32, 3 * k + 1 + 2 * mf))
+        for t, dt, numel in want:
+            if t.dtype != dt or t.numel() != numel or not t.is_contiguous() or not t.is_cuda or t.device != res.device:
+                raise CavpError("SemanticValidation: device buffers of the wrong dtype, size or device")
+        self.device = res.device
+        self._res, self._scratch, self._last = res, scratch, last
+        self._state = res[:sw]
+        self._acc = res[sw:].view(torch.float32)[:3 * k + 1]
+
+    def _ensure(self):
+        if self._res is None:
+            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            if dev.type != "cuda":
+                raise CavpError("SemanticValidation lives on a HIP device (there is no CPU fallback)")
+            if torch.cuda.is_current_stream_capturing():
+                raise CavpError("SemanticValidation would allocate during hipGraph capture; run one eager update first")
+            k, mf = self.num_classes, self.max_frames
+            self._bind(_zeros((ops.SEMVAL_STATE_WORDS + (3 * k + 2) // 2,), torch.int64, dev), _zeros((mf, self.words), torch.int32, dev),
+                       _zeros((3 * k + 1 + 2 * mf,), torch.float32, dev))
+
+    # ---- the updates -------------------------------------------------------------------------------------------------------
+    def _check_labels(self, labels, count):
+        """(B, T, H, W) of the labels and the optional count."""
+        E = CavpError
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() not in (3, 4):
+            raise E(f"SemanticValidation: labels must be an int64 tensor [B, T, H, W] (or [N, H, W] without count), got "
+                    f"{getattr(labels, 'dtype', type(labels))} {tuple(getattr(labels, 'shape', ()))}")
+        if labels.dim() == 3 and count is not None:
+            raise E("SemanticValidation: count needs labels [B, T, H, W]")
+        B, T = (labels.shape[0], labels.shape[1]) if labels.dim() == 4 else (1, labels.shape[0])
+        H, W = labels.shape[-2:]
+        if B * T < 1 or H < 1 or W < 1:
+            raise E("SemanticValidation: empty labels are not supported")
+        if B * T > self.max_frames:
+            raise E(f"SemanticValidation: {B * T} frames in one update, max_frames = {self.max_frames}")
+        if count is not None:
+            if not isinstance(count, torch.Tensor) or count.dtype not in (torch.int32, torch.int64) or tuple(count.shape) != (B,):
+                raise E(f"SemanticValidation: count must be an int32 or int64 tensor of shape ({B},)")
+        if not labels.is_contiguous() or (count is not None and not count.is_contiguous()):
+            raise E("SemanticValidation: dense (contiguous) tensors required")
+        return B, T, H, W
+
+    def _launch(self, pred, is_mask, labels, count, B, T, c, hw):
+        self._ensure()
+        for t in (pred, labels, count):
+            if t is not None and t.device != self.device:
+                raise CavpError(f"SemanticValidation lives on {self.device}, got a tensor on {t.device}")
+        ops.semval_update(pred, is_mask, labels, count, B, T, c, hw, self.num_classes, self.max_frames, self._scratch, self._acc,
+                          self._last, self._state)
+        self._last_frames = B * T
+
+    def update(self, pred: torch.Tensor, labels: torch.Tensor, count=None) -> None:
+        """Score one batch of clips (see the class docstring): two launches, no host sync; graph replays of a captured update()
+        accumulate the same way."""
+        B, T, H, W = self._check_labels(labels, count)
+        N, k = B * T, self.num_classes
+        if not isinstance(pred, torch.Tensor):
+            raise CavpError("SemanticValidation: pred is a tensor")
+        is_mask = pred.dtype == torch.uint8
+        if is_mask:
+            if tuple(pred.shape) != (N, H, W):
+                raise CavpError(f"SemanticValidation: a uint8 class mask of shape {(N, H, W)} required, got {tuple(pred.shape)}")
+            c = 0
+        elif pred.dtype == torch.float32:
+            if pred.dim() != 4 or pred.shape[0] != N or tuple(pred.shape[2:]) != (H, W):
+                raise CavpError(f"SemanticValidation: float32 logits [{N}, {k}, {H}, {W}] required, got {tuple(pred.shape)}")
+            c = pred.shape[1]
+            if c != k:
+                raise CavpError(f"SemanticValidation: the logits have {c} channels, num_classes is {k}: the metric takes its class "
+                                f"number from the logits")
+        else:
+            raise CavpError(f"SemanticValidation: pred is a uint8 class mask [N, H, W] or float32 logits [N, K, H, W], got {pred.dtype}")
+        if not pred.is_contiguous():
+            raise CavpError("SemanticValidation: dense (contiguous) tensors required")
+        ops._need_gpu(pred, labels, count)
+        self._launch(pred.detach(), is_mask, labels, count, B, T, c, H * W)
+
+    def update_lowres(self, lo: torch.Tensor, labels: torch.Tensor, count=None, input_shape=None, align_corners: bool = False) -> None:
+        """update() from the low-resolution logits `lo` (NHWC view [B*T, h, w, K], f32 or bf16: CAVP.predict_lowres): the result of
+        update(full_res_logits, ...), bit for bit, where full_res_logits is the bilinear upsample of `lo` to `input_shape` (default
+        labels.shape[-2:]), which is never materialised: ops.seg_predict writes the uint8 class mask of all B*T frames, the frame
+        kernel reads the participating ones.  K <= 256 (a byte mask).  Three launches, no host sync, no allocation after the first
+        call with a given (B*T, H, W)."""
+        B, T, H, W = self._check_labels(labels, count)
+        if not isinstance(lo, torch.Tensor) or lo.dim() != 4 or lo.shape[0] != B * T or lo.dtype not in (torch.float32, torch.bfloat16):
+            raise CavpError(f"SemanticValidation: low-res logits [{B * T}, h, w, K] (float32 or bfloat16) required, got "
+                            f"{getattr(lo, 'dtype', type(lo))} {tuple(getattr(lo, 'shape', ()))}")
+        shape = (H, W) if input_shape is None else tuple(int(v) for v in input_shape)
+        if shape != (H, W):
+            raise CavpError(f"SemanticValidation: input_shape {shape} differs from the labels' {(H, W)}")
+        c = lo.shape[3]
+        if c != self.num_classes or c > 256:
+            raise CavpError(f"SemanticValidation: the low-res logits have {c} channels, num_classes is {self.num_classes} (and at "
+                            f"most 256: a byte mask)")
+        ops._need_gpu(lo, labels, count)
+        self._ensure()
+        if lo.device != self.device:
+            raise CavpError(f"SemanticValidation lives on {self.device}, got a tensor on {lo.device}")
+        key = (B * T, H, W)
+        if key not in self._lowres:
+            if torch.cuda.is_current_stream_capturing():
+                raise CavpError("SemanticValidation.update_lowres would allocate during hipGraph capture; run one eager call first")
+            self._lowres[key] = torch.empty(key, dtype=torch.uint8, device=self.device)
+        mask = self._lowres[key]
+        ops.seg_predict(lo.detach(), shape, mask=mask, align_corners=align_corners)
+        self._launch(mask, True, labels, count, B, T, 0, H * W)
+
+    # ---- reading -----------------------------------------------------------------------------------------------------------
+    def accumulators(self) -> torch.Tensor:
+        """float32 [3, K] on the device: ious | fscores | cls_count, the running sums over all updates (a view; zeros on the CPU
+        before the first update)."""
+        k = self.num_classes
+        if self._res is None:
+            return torch.zeros((3, k), dtype=torch.float32)
+        return self._acc[:3 * k].view(3, k)
+
+    def last_call(self):
+        """(ious [K], fscores [K], cls_count [K], frame_miou [N]) of the last update as float32 device views: what one call of the
+        reference's calc_color_miou_fscore on that batch returns.  frame_miou reads -1 for a frame that took no part."""
+        if self._res is None:
+            raise CavpError("last_call: no SemanticValidation update yet")
+        k = self.num_classes
+        return (self._last[:k], self._last[k:2 * k], self._last[2 * k:3 * k], self._last[3 * k + 1:3 * k + 1 + self._last_frames])
+
+    def frames(self) -> int:
+        """Frames scored so far: one host read."""
+        return 0 if self._res is None else int(self._state[2].item())
+
+    @staticmethod
+    def _finish(ious: torch.Tensor, fscores: torch.Tensor, cls_count: torch.Tensor, binary_sum: torch.Tensor, frames: int) -> dict:
+        """The benchmark driver's reduction of the float32 host accumulators (see the class docstring)."""
+        if frames < 1:
+            raise CavpError("SemanticValidation: no frame counted yet")
+        miou_pc, fscore_pc = ious / cls_count, fscores / cls_count
+        miou_pc[miou_pc != miou_pc] = 0
+        fscore_pc[fscore_pc != fscore_pc] = 0
+        miou, fscore = miou_pc.mean(), fscore_pc.mean()
+        binary = binary_sum / torch.tensor(frames, dtype=torch.float32)
+        return {"miou": miou.item(), "fscore": fscore.item(), "jf": ((miou + fscore) / 2).item(), "binary_miou": binary.item(),
+                "miou_pc": miou_pc, "fscore_pc": fscore_pc, "cls_count": cls_count.clone()}
+
+    def results(self) -> dict:
+        """{"miou", "fscore", "jf", "binary_miou"} as Python floats and {"miou_pc", "fscore_pc", "cls_count"} as float32 [K] host
+        tensors, from ONE host copy.  Raises CavpError when no frame has been counted."""
+        if self._res is None:
+            raise CavpError("SemanticValidation: no frame counted yet")
+        host = self._res.cpu()
+        k, sw = self.num_classes, ops.SEMVAL_STATE_WORDS
+        acc = host[sw:].view(torch.float32)
+        return self._finish(acc[:k], acc[k:2 * k], acc[2 * k:3 * k], acc[3 * k], int(host[2]))
+
+    def reset(self) -> None:
+        """Zero the accumulators and the frame counter (the bad-input counters stay until check())."""
+        if self._res is not None:
+            _zero_(self._res[2:])
+
+    def check(self) -> None:
+        """Synchronises and raises CavpError if, since the last check, a mask byte was >= num_classes or a count outside [0, T]."""
+        if self._res is None:
+            raise CavpError("check: no SemanticValidation update yet")
+        bad = self._state[:2].cpu().tolist()
+        if any(bad):
+            _zero_(self._state[:2])
+            raise CavpError(f"SemanticValidation: {bad[0]} mask value(s) >= {self.num_classes}, {bad[1]} count(s) outside [0, T] "
+                            f"since the last check")
+
+
+_semval_private = {}
+
+
+def _semval_call(pred: torch.Tensor, target: torch.Tensor) -> numpy.ndarray:
+    """One update of a private SemanticValidation on (pred [BF, C, H, W] logits, target [BF, H, W]) and ONE host read: the float32
+    host copy of its last-call buffer ious | fscores | cls_count | binary sum | frame_miou [BF] | ..."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor) or pred.dim() != 4 or target.dim() != 3:
+        raise CavpError("avsbench metrics: pred [BF, C, H, W] logits and target [BF, H, W] required")
+    ops._need_gpu(pred, target)
+    k, n = pred.shape[1], pred.shape[0]
+    key = (k, pred.device)
+    sv = _semval_private.get(key)
+    if sv is None or sv.max_frames < n:
+        sv = _semval_private[key] = SemanticValidation(k, max_frames=max(n, 1), device=pred.device)
+    sv.update(pred.float().contiguous(), target.long().contiguous())
+    return sv._last.cpu()
+
+
+def calc_color_miou_fscore(pred, target, T=10):
+    """The reference's calc_color_miou_fscore: (ious [C], fscores [C], cls_count [C], vid_miou_list) - the per-class sums of the
+    per-frame IoU and F-score (beta^2 = 0.3) over the BF frames and the number of frames each class occurs in, as float32 host
+    tensors, and the list of the BF per-frame mean IoUs (0-d float32 host tensors).  pred: device logits [BF, C, H, W]; target:
+    [BF, H, W] class indices.  T is accepted and unused, as in the reference."""
+    host = _semval_call(pred, target)
+    k, n = pred.shape[1], pred.shape[0]
+    return host[:k].clone(), host[k:2 * k].clone(), host[2 * k:3 * k].clone(), list(host[3 * k + 1:3 * k + 1 + n].clone().unbind(0))
+
+
+def calc_color_miou(pred, target, T=10):
+    """The reference's calc_color_miou: (ious [C], cls_count [C]) of calc_color_miou_fscore."""
+    host = _semval_call(pred, target)
+    k = pred.shape[1]
+    return host[:k].clone(), host[2 * k:3 * k].clone()
+
+
+def calc_binary_miou(pred, target, eps=1e-7, size_average=True):
+    """The reference's calc_binary_miou: the mean over the N frames of the IoU of (argmax != 0) against (target != 0), an empty
+    target scoring its background overlap over all pixels, as a 0-d float32 host tensor.  eps is fixed at the default 1e-7;
+    size_average is accepted and unused, as in the reference."""
+    if eps != 1e-7:
+        raise CavpError("calc_binary_miou: eps is fixed at 1e-7 on the device")
+    host = _semval_call(pred, target)
+    return host[3 * pred.shape[1]] / torch.tensor(pred.shape[0], dtype=torch.float32)

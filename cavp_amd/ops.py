@@ -621,6 +621,37 @@ def clipval_update(pred: torch.Tensor, is_mask: bool, labels: torch.Tensor, coun
                                         _ptr(counts), _ptr(frames), _ptr(state), st), f"cavp_clipval_combine B{B} T{T} K{k}")
 
 
+SEMVAL_STATE_WORDS = 4             # {mask bytes >= K, bad counts, frames, ticket}
+
+
+def semval_update(pred: torch.Tensor, is_mask: bool, labels: torch.Tensor, count: Optional[torch.Tensor], B: int, T: int, c: int, hw: int,
+                  k: int, max_frames: int, scratch: torch.Tensor, acc: torch.Tensor, last: torch.Tensor, state: torch.Tensor,
+                  combine: bool = True) -> None:
+    """One SemanticValidation update of inputs that metrics.SemanticValidation has checked (include/cavp_hip.h,
+    cavp_semval_frame_counts and cavp_semval_combine): the frames' class areas and binary sums into the scratch [max_frames, 3K + 4],
+    then the float32 tail into acc [3K + 1], last [3K + 1 + 2 * max_frames] and state [4].  combine=False stops after the first
+    launch and leaves the integer counts in the scratch (the tests read them there, from a scratch of their own)."""
+    E = _lib.CavpError
+    if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() != max_frames * (3 * k + 4):
+        raise E("semval_update: scratch must be a dense int32 [max_frames, 3K + 4] tensor")
+    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != 3 * k + 1:
+        raise E("semval_update: acc must be a dense float32 [3K + 1] tensor")
+    if last.dtype != torch.float32 or not last.is_contiguous() or last.numel() != 3 * k + 1 + 2 * max_frames:
+        raise E("semval_update: last must be a dense float32 [3K + 1 + 2 * max_frames] tensor")
+    if state.dtype != torch.int64 or not state.is_contiguous() or state.numel() != SEMVAL_STATE_WORDS:
+        raise E(f"semval_update: state must be a dense int64 [{SEMVAL_STATE_WORDS}] tensor")
+    if B * T > max_frames:
+        raise E(f"semval_update: {B * T} frames, max_frames = {max_frames}")
+    _need_gpu(pred, labels, count, scratch, acc, last, state)
+    lib, st = _lib.load(), C.c_void_p(_stream())
+    i64 = 1 if count is not None and count.dtype == torch.int64 else 0
+    _lib.check(lib.cavp_semval_frame_counts(_ptr(pred), 1 if is_mask else 0, _ptr(labels), _ptr(count), i64, B, T, c, hw, k,
+                                            _ptr(scratch), _ptr(state), st), f"cavp_semval_frame_counts B{B} T{T} C{c} HW{hw} K{k}")
+    if combine:
+        _lib.check(lib.cavp_semval_combine(_ptr(scratch), _ptr(count), i64, B, T, hw, k, max_frames, _ptr(acc), _ptr(last),
+                                           _ptr(state), st), f"cavp_semval_combine B{B} T{T} K{k}")
+
+
 VIDEOVAL_MAX_THRESHOLDS = 1024     # CAVP_VIDEOVAL_MAX_THRESHOLDS
 VIDEOVAL_STATE_WORDS = 8           # {labels outside {0, 1, ignore}, mask bytes >= K, bad counts, videos dropped, videos seen, ticket, -, -}
 

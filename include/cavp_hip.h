@@ -961,6 +961,44 @@ int cavp_videoval_frame_stats(const void* pred, int32_t pred_is_mask, const floa
 int cavp_videoval_combine(int64_t* stats, uint32_t* hist, const void* count, int32_t count_i64, int32_t B, int32_t T, int64_t HW,
                           int32_t pr_num, int32_t max_videos, float* J, float* F, int64_t* state, void* stream);
 
+/* ---- Semantic validation (two entry points added to ABI 16; nothing else changed): the per-frame, per-class IoU and F-score
+ * (beta^2 = 0.3) of the AVSBench-semantic metric (utils/avsbench_metrics.py: calc_color_miou_fscore, calc_color_miou,
+ * calc_binary_miou) for a batch of B clips of T frames at once, restated in tests/_semval_ref.py ----
+ * Frame n = b * T + t takes part iff t < clamp(count[b], 0, T) (count as for clip validation above; NULL: all frames).  A frame
+ * that does not take part is not read.  Every pixel of a participating frame has a label v (labels: dense int64 [B*T][HW], never
+ * written) and a prediction p: pred_is_mask == 0: pred is dense f32 logits [B*T][K][HW] (C must equal K: the metric takes its
+ * class number from the logits; any 4-byte aligned base), p = argmax over K (first maximal index, a NaN counts as the maximum; the
+ * reference's softmax in front of it does not change it and is not computed); pred_is_mask != 0: pred is a dense u8 class mask
+ * [B*T][HW] (C is ignored).  16-byte loads when HW % 4 == 0 and the bases are aligned (mask: 4 bytes), element loads otherwise.
+ *
+ * cavp_semval_frame_counts adds, per participating frame, into the per-frame scratch [n][3K + 4] (u32, u32 atomics):
+ *   inter[c] = #(p == c and v == c), pred[c] = #(p == c and v >= 0), lab[c] = #(v == c) at [n][c], [n][K + c], [n][2K + c]: the
+ *   three torch.histc(bins=K, min=1, max=K) areas of the reference.  A pixel with v < 0 counts in none; one with v >= K (the ignore
+ *   value 255 included) counts in pred only, as in the reference, whose histc drops the label.
+ *   [n][3K ..]: #(P and G), #(P or G), #(not P and not G), #G over ALL pixels with P = (p != 0), G = (v != 0): calc_binary_miou.
+ *   A mask byte p >= K is counted in state[0] and sets none of the class counters (it is foreground in the binary sums): no label
+ *   or mask value indexes memory unguarded.  Counters are privatised per workgroup in LDS (3K + 4 words, at most 48 KiB + 16 bytes).
+ * cavp_semval_combine, one thread per class c, float32, IEEE operations, no contraction, frames in ascending n:
+ *   union = pred + lab - inter, iou = inter / (2.220446049250313e-16f + union), precision = inter / pred, recall = inter / lab,
+ *   f = ((1.3f * precision) * recall) / (0.3f * precision + recall) with NaN -> 0, hit = (union != 0).
+ *   last[c], last[K + c], last[2K + c] = the sums of iou, f and hit over the call's participating frames, starting from zero (one
+ *   call of calc_color_miou_fscore); acc[c], acc[K + c], acc[2K + c] += those sums (the benchmark driver's `miou_pc += _miou_pc`).
+ *   Per frame: last[3K + 1 + n] = frame_miou = (sum over c ascending of iou) / #(iou != 0) (NaN when no IoU is non-zero), -1 for a
+ *   frame that takes no part; last[3K + 1 + max_frames + n] = the frame's binary IoU = inter / (union + 1e-7f) with (inter, union)
+ *   = (#(P and G), #(P or G)), or (#(not P and not G), HW) when #G == 0; -1 likewise.  last[3K] = the sum of the binary IoUs in
+ *   ascending n from zero, acc[3K] += it, state[2] += the number of participating frames, state[1] += the count[b] outside [0, T].
+ *   acc: f32 [3K + 1], last: f32 [3K + 1 + 2 * max_frames], B*T <= max_frames.  Writes the scratch of the participating frames
+ *   back to zero (the last workgroup to finish, by a ticket in state[3] that it leaves at 0).
+ * scratch must hold at least B*T frames and be ZERO before the first call; combine leaves it zero, so nothing is cleared outside
+ * the launches.  state: int64 [4] (device, persistent) {mask bytes >= K, bad counts, frames, ticket}.  Launch order on one stream:
+ * frame_counts, combine, with the same count, B, T, HW and K.  2 <= K <= CAVP_METRICS_MAX_CLASSES, B*T <= 65535, HW < 2^31 (the
+ * counts are exact as float32 below 2^24 pixels per frame).  The integer counts are independent of arrival order, the float tail
+ * runs in a fixed order.  No allocation, no synchronisation, no host read of a device value: capturable in a hipGraph. */
+int cavp_semval_frame_counts(const void* pred, int32_t pred_is_mask, const int64_t* labels, const void* count, int32_t count_i64,
+                             int32_t B, int32_t T, int32_t C, int64_t HW, int32_t K, uint32_t* scratch, int64_t* state, void* stream);
+int cavp_semval_combine(uint32_t* scratch, const void* count, int32_t count_i64, int32_t B, int32_t T, int64_t HW, int32_t K,
+                        int32_t max_frames, float* acc, float* last, int64_t* state, void* stream);
+
 /* ---- Wave stage (two entry points added to ABI 16; nothing else changed): the mono 16 kHz window the reference's data sets cut
  * on the host from a decoded file - Resample(rate, 16000), crop_audio, the sum over the sources resp. the mean over the channels,
  * the one second of a clip (vpo_mono/multi_source/audio/audio_dataset.py:48-70, avss/audio/audio_dataset.py:42-62,
