@@ -101,6 +101,16 @@ PROTOTYPES = {
     "cavp_grad_guard_finish": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "cavp_optimizer_schedule_guarded": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "cavp_optimizer_step_guarded": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp]),
+    # gradient accumulation: the accumulate launch, the state advance and the gated twins of the six launches above (added to ABI 16)
+    "cavp_accum_state_bytes": (C.c_int64, []),
+    "cavp_grad_accumulate": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "cavp_accum_advance": (_i32, [_vp, _vp, _vp, _vp]),
+    "cavp_optimizer_schedule_gated": (_i32, [_vp, _vp, _vp]),
+    "cavp_optimizer_step_dev_gated": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "cavp_grad_guard_partials_gated": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "cavp_grad_guard_finish_gated": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "cavp_optimizer_schedule_guarded_gated": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "cavp_optimizer_step_guarded_gated": (_i32, [_vp, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
     # step rollback: table-driven save and guarded restore of the state a forward mutates (added to ABI 16)
     "cavp_rollback_range_bytes": (C.c_int64, []),
     "cavp_rollback_state_bytes": (C.c_int64, []),

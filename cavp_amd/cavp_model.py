@@ -953,7 +953,7 @@ class CAVP(nn.Module):
 
     def capture_train_step(self, image, audio, label, ignore_index: int = 255, loss_scale: float = 1.0,
                            split: Optional[bool] = None, contrast=None, label_shuffle=None, contrast_weight: float = 1.0,
-                           optimizer=None, prologue=None, rollback=None):
+                           optimizer=None, prologue=None, rollback=None, accumulate=None):
         """Capture forward_train + CE + backward (about 1000 kernel launches) into hipGraphs and return
         `replay() -> loss`.  `image`, `audio`, `label` are the static input buffers: copy new batches into them before
         each replay.  Weight packing is part of the graph, so replays always see the current parameters.
@@ -991,8 +991,18 @@ class CAVP(nn.Module):
         step the guard skips leaves every registered range as it found it.  The warm-up passes are undone the same way, each by
         an unconditional restore() behind it and one more behind the capture, so the BatchNorm statistics, the bank and the call
         counters are where they were when this returns and nothing needs reseeding; the rollback's counters are zeroed last, so
-        stats() counts replays only."""
+        stats() counts replays only.
+        accumulate: a cavp_amd.accumulate.GradAccumulator built on `optimizer` (N = its micro_steps).  The passes then run with
+        loss_scale / N and the captured one records `accumulate.step(losses=...)` in the update's place: N - 1 of N replays only add
+        their gradients to the accumulator, the N-th sums the window into the arena and guards, schedules and updates on it (t and the
+        schedule's lengths count windows).  After a replay `p.grad` holds that micro-batch's gradient, after a window's last replay the
+        window's sum; the returned loss is the micro-batch's.  The warm-up passes and the capture leave the accumulator and its k
+        alone.  Not with `rollback=` and not with collectives on."""
+        from .accumulate import check_capture
         from .train import _no_gc_during_capture, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world
+        micro_steps = check_capture(accumulate, optimizer, rollback, collectives_on())
+        if micro_steps is not None:
+            loss_scale = loss_scale / micro_steps   # the head applies the scale in f32
         if optimizer is not None:
             if getattr(optimizer, "_sched", None) is None:
                 raise CavpError("capture_train_step: only an optimiser with the device schedule can be recorded "
@@ -1039,12 +1049,13 @@ class CAVP(nn.Module):
         def step_update(loss):
             # a StepGuard's record carries the step's losses: (l_ce, l_ctr) with the contrast term, else the loss itself; the
             # captured pass's tensors are the ones every replay writes, so they are taken once
+            step = optimizer.step if accumulate is None else accumulate.step
             if getattr(optimizer, "_guard", None) is None:
-                optimizer.step()
+                step()
                 return
             if not static_losses:
                 static_losses.append(tuple(self._last_losses) if contrast is not None else (loss,))
-            optimizer.step(losses=static_losses[0])
+            step(losses=static_losses[0])
             if rollback is not None:
                 rollback.restore_if_skipped(optimizer._guard)   # directly behind the guarded update, on its stream
 

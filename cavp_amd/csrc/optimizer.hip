@@ -156,8 +156,8 @@ __device__ __forceinline__ void guard_acc4(const float4& g, float& ss, int& nf) 
 
 // The update's block -> job mapping and element -> thread mapping; the gradients of the block are read once.  f32 tree: 2 levels
 // inside a float4, 2 over a thread's four float4, 6 over the wave, 2 over the four waves = 12 levels, no chain.
-__global__ __launch_bounds__(256) void grad_guard_partials_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
-                                                                  cavp_guard_partial* __restrict__ partials) {
+__device__ __forceinline__ void grad_guard_partials_body(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                         cavp_guard_partial* __restrict__ partials) {
   __shared__ float s_ss[4];
   __shared__ int s_nf[4];
   const cavp_opt_job J = jobs[job_of_block(jobs, njobs)];
@@ -206,15 +206,19 @@ __global__ __launch_bounds__(256) void grad_guard_partials_kernel(const cavp_opt
   }
 }
 
+__global__ __launch_bounds__(256) void grad_guard_partials_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                                  cavp_guard_partial* __restrict__ partials) {
+  grad_guard_partials_body(jobs, njobs, partials);
+}
+
 constexpr int kFinishThreads = 1024, kFinishWaves = kFinishThreads / 64;
 
 // One workgroup of 16 waves.  Wave w takes the jobs w, w + 16, ...; lane l adds that job's partials l, l + 64, ... in double, a
 // butterfly adds the 64 lanes, the wave adds its jobs in ascending order, thread 0 adds the waves in ascending order: the order
 // is a function of the job table alone.
-__global__ __launch_bounds__(kFinishThreads) void grad_guard_finish_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
-                                                                           int total_blocks,
-                                                                           const cavp_guard_partial* __restrict__ partials,
-                                                                           cavp_guard_state* __restrict__ guard) {
+__device__ __forceinline__ void grad_guard_finish_body(const cavp_opt_job* __restrict__ jobs, int njobs, int total_blocks,
+                                                       const cavp_guard_partial* __restrict__ partials,
+                                                       cavp_guard_state* __restrict__ guard) {
   __shared__ double s_ss[2][kFinishWaves];
   __shared__ long long s_nf[kFinishWaves];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -270,10 +274,16 @@ __global__ __launch_bounds__(kFinishThreads) void grad_guard_finish_kernel(const
   guard->skip = (guard->skip_nonfinite & CAVP_GUARD_SKIP_GRADIENTS) != 0 && (total_nf > 0 || !isfinite(norm));
 }
 
+__global__ __launch_bounds__(kFinishThreads) void grad_guard_finish_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                                           int total_blocks,
+                                                                           const cavp_guard_partial* __restrict__ partials,
+                                                                           cavp_guard_state* __restrict__ guard) {
+  grad_guard_finish_body(jobs, njobs, total_blocks, partials, guard);
+}
+
 // One thread, behind the finish launch on the stream.
-__global__ void optimizer_schedule_guarded_kernel(cavp_opt_state* state, cavp_guard_state* guard, const float* loss0,
-                                                  const float* loss1) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+__device__ __forceinline__ void schedule_guarded_body(cavp_opt_state* state, cavp_guard_state* guard, const float* loss0,
+                                                      const float* loss1) {
   const float l0 = loss0 ? loss0[0] : 0.f, l1 = loss1 ? loss1[0] : 0.f;
   int skip = guard->skip;
   // CAVP_GUARD_SKIP_LOSSES (a switch of its own): a loss that is not finite skips too.  The CE head turns "every label ignored"
@@ -307,12 +317,70 @@ __global__ void optimizer_schedule_guarded_kernel(cavp_opt_state* state, cavp_gu
   guard->head = head + 1;
 }
 
+__global__ void optimizer_schedule_guarded_kernel(cavp_opt_state* state, cavp_guard_state* guard, const float* loss0,
+                                                  const float* loss1) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  schedule_guarded_body(state, guard, loss0, loss1);
+}
+
 // the update with clip_coef * g; a skipped step returns before it touches a parameter or a state buffer
 __global__ __launch_bounds__(256) void optimizer_step_guarded_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
                                                                      float momentum, float eps,
                                                                      const cavp_opt_state* __restrict__ state,
                                                                      const cavp_guard_state* __restrict__ guard) {
   if (guard->skip) return;
+  optimizer_step_body<true>(jobs, njobs, state->lr_sgd, state->lr_adam, momentum, state->beta1, state->beta2, eps, state->bc1,
+                            state->bc2_sqrt, state->first_step, guard->clip_coef);
+}
+
+// ---- gated twins (gradient accumulation, grad_accum.hip) -------------------------------------------------------------------------
+// The six device-schedule kernels once more, each behind one word: *gate == 0 (a micro-step that does not close its window) and
+// every workgroup returns before it reads or writes anything else; otherwise the SAME device bodies run, so a closing micro-step
+// gives the bits of the ungated launch on an equal state.  The word is written by the accumulator's advance launch, earlier on
+// the stream, and is read-only here: uniform over the launch, no workgroup depends on another.
+
+__global__ void optimizer_schedule_gated_kernel(cavp_opt_state* state, const int32_t* __restrict__ gate) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || *gate == 0) return;
+  schedule_advance(state);
+}
+
+__global__ __launch_bounds__(256) void optimizer_step_dev_gated_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                                       float momentum, float eps,
+                                                                       const cavp_opt_state* __restrict__ state,
+                                                                       const int32_t* __restrict__ gate) {
+  if (*gate == 0) return;
+  optimizer_step_body<false>(jobs, njobs, state->lr_sgd, state->lr_adam, momentum, state->beta1, state->beta2, eps, state->bc1,
+                             state->bc2_sqrt, state->first_step);
+}
+
+__global__ __launch_bounds__(256) void grad_guard_partials_gated_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                                        cavp_guard_partial* __restrict__ partials,
+                                                                        const int32_t* __restrict__ gate) {
+  if (*gate == 0) return;
+  grad_guard_partials_body(jobs, njobs, partials);
+}
+
+__global__ __launch_bounds__(kFinishThreads) void grad_guard_finish_gated_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                                                 int total_blocks,
+                                                                                 const cavp_guard_partial* __restrict__ partials,
+                                                                                 cavp_guard_state* __restrict__ guard,
+                                                                                 const int32_t* __restrict__ gate) {
+  if (*gate == 0) return;
+  grad_guard_finish_body(jobs, njobs, total_blocks, partials, guard);
+}
+
+__global__ void optimizer_schedule_guarded_gated_kernel(cavp_opt_state* state, cavp_guard_state* guard, const float* loss0,
+                                                        const float* loss1, const int32_t* __restrict__ gate) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || *gate == 0) return;
+  schedule_guarded_body(state, guard, loss0, loss1);
+}
+
+__global__ __launch_bounds__(256) void optimizer_step_guarded_gated_kernel(const cavp_opt_job* __restrict__ jobs, int njobs,
+                                                                           float momentum, float eps,
+                                                                           const cavp_opt_state* __restrict__ state,
+                                                                           const cavp_guard_state* __restrict__ guard,
+                                                                           const int32_t* __restrict__ gate) {
+  if (*gate == 0 || guard->skip) return;
   optimizer_step_body<true>(jobs, njobs, state->lr_sgd, state->lr_adam, momentum, state->beta1, state->beta2, eps, state->bc1,
                             state->bc2_sqrt, state->first_step, guard->clip_coef);
 }
@@ -377,5 +445,54 @@ extern "C" int cavp_optimizer_step_guarded(const cavp_opt_job* jobs_device, int3
   if (!jobs_device || !state_device || !guard_device || njobs <= 0 || total_blocks <= 0) return CAVP_ERR_BAD_ARG;
   optimizer_step_guarded_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(jobs_device, njobs, momentum, eps, state_device,
                                                                                guard_device);
+  CHECK_LAUNCH();
+}
+
+// ---- gated entry points: the launches above with the accumulator's gate word (cavp_accum_state.gate) ---------------------------
+extern "C" int cavp_optimizer_schedule_gated(cavp_opt_state* state_device, const int32_t* gate_device, void* stream) {
+  if (!state_device || !gate_device) return CAVP_ERR_BAD_ARG;
+  optimizer_schedule_gated_kernel<<<1, 1, 0, (hipStream_t)stream>>>(state_device, gate_device);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_optimizer_step_dev_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum,
+                                             float eps, const cavp_opt_state* state_device, const int32_t* gate_device,
+                                             void* stream) {
+  if (!jobs_device || !state_device || !gate_device || njobs <= 0 || total_blocks <= 0) return CAVP_ERR_BAD_ARG;
+  optimizer_step_dev_gated_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(jobs_device, njobs, momentum, eps, state_device,
+                                                                                 gate_device);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_grad_guard_partials_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks,
+                                              cavp_guard_partial* partials, const int32_t* gate_device, void* stream) {
+  if (!jobs_device || !partials || !gate_device || njobs <= 0 || total_blocks <= 0) return CAVP_ERR_BAD_ARG;
+  grad_guard_partials_gated_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(jobs_device, njobs, partials, gate_device);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_grad_guard_finish_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks,
+                                            const cavp_guard_partial* partials, cavp_guard_state* guard_device,
+                                            const int32_t* gate_device, void* stream) {
+  if (!jobs_device || !partials || !guard_device || !gate_device || njobs <= 0 || total_blocks <= 0) return CAVP_ERR_BAD_ARG;
+  grad_guard_finish_gated_kernel<<<1, kFinishThreads, 0, (hipStream_t)stream>>>(jobs_device, njobs, total_blocks, partials,
+                                                                                 guard_device, gate_device);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_optimizer_schedule_guarded_gated(cavp_opt_state* state_device, cavp_guard_state* guard_device,
+                                                     const float* loss0, const float* loss1, const int32_t* gate_device,
+                                                     void* stream) {
+  if (!state_device || !guard_device || !gate_device) return CAVP_ERR_BAD_ARG;
+  optimizer_schedule_guarded_gated_kernel<<<1, 1, 0, (hipStream_t)stream>>>(state_device, guard_device, loss0, loss1, gate_device);
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_optimizer_step_guarded_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks,
+                                                 float momentum, float eps, const cavp_opt_state* state_device,
+                                                 const cavp_guard_state* guard_device, const int32_t* gate_device, void* stream) {
+  if (!jobs_device || !state_device || !guard_device || !gate_device || njobs <= 0 || total_blocks <= 0) return CAVP_ERR_BAD_ARG;
+  optimizer_step_guarded_gated_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(jobs_device, njobs, momentum, eps,
+                                                                                     state_device, guard_device, gate_device);
   CHECK_LAUNCH();
 }

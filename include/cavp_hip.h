@@ -532,6 +532,53 @@ int cavp_optimizer_schedule_guarded(cavp_opt_state* state_device, cavp_guard_sta
 int cavp_optimizer_step_guarded(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum, float eps,
                                 const cavp_opt_state* state_device, const cavp_guard_state* guard_device, void* stream);
 
+/* Gradient accumulation (added to ABI 16): n micro-batches per optimiser update, with nothing taken from the host, so that the
+ * captured step can run "7 of 8 replays only accumulate, the 8th also guards, schedules and updates".  The accumulator is a flat
+ * f32 buffer with the gradient arena's layout (an element lives at its gradient's offset from arena_base; both bases 16-byte
+ * aligned, the accumulator at least as long as the arena).  One micro-step is, on one stream:
+ *   cavp_grad_accumulate -> cavp_accum_advance -> the gated twins of the optimiser's launches, in the ungated order.
+ * The host fills n (>= 1) and k (the index of the next micro-step in its window, 0 <= k < n) and zeroes the rest. */
+typedef struct cavp_accum_state {
+  int32_t n;             /* micro-steps per window */
+  int32_t k;             /* index of the next micro-step in the window */
+  int32_t gate;          /* from here on: written by the device.  1 while the current micro-step closes a window */
+  int32_t pad_;
+  int64_t windows;       /* windows closed so far */
+  int64_t micro_total;   /* micro-steps so far */
+  float loss_sum0;       /* running f32 sums of the two loss words over the window, in micro-step order */
+  float loss_sum1;
+  float loss_mean0;      /* the last closed window's means: sum / n, correctly rounded */
+  float loss_mean1;
+} cavp_accum_state;
+int64_t cavp_accum_state_bytes(void);
+/* One workgroup per optimiser block (the update's job table and block map).  With g the gradients in the arena and k, n loaded
+ * from the state block: k == 0: acc <- g (a copy; the accumulator is not read);  0 < k < n - 1: acc <- acc + g;
+ * k == n - 1: g <- acc + g (the window's sum goes back into the arena);  n == 1: returns at once.  One IEEE f32 add per element
+ * and micro-step.  Reads the state block only; no atomics, no workgroup depends on another.  Gradients outside the job table
+ * and the padding between views are not touched. */
+int cavp_grad_accumulate(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, const float* arena_base,
+                         float* acc_base, const cavp_accum_state* state_device, void* stream);
+/* One thread, behind the accumulate launch: gate = (k == n - 1); for each given loss word sum = (k == 0 ? l : sum + l) and, when
+ * the window closes, mean = sum / n; then k = (k + 1) mod n, micro_total + 1, windows + gate.  loss0 / loss1: optional 1-element
+ * f32 device arrays. */
+int cavp_accum_advance(cavp_accum_state* state_device, const float* loss0, const float* loss1, void* stream);
+/* Gated twins of the six device-schedule launches above: gate_device points at cavp_accum_state.gate.  Zero: every workgroup
+ * returns at once and nothing is written (no record, no skipped_total, t, rates, parameters and state buffers untouched);
+ * otherwise the ungated launch's device code runs, so equal states give equal bits. */
+int cavp_optimizer_schedule_gated(cavp_opt_state* state_device, const int32_t* gate_device, void* stream);
+int cavp_optimizer_step_dev_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum, float eps,
+                                  const cavp_opt_state* state_device, const int32_t* gate_device, void* stream);
+int cavp_grad_guard_partials_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks,
+                                   cavp_guard_partial* partials, const int32_t* gate_device, void* stream);
+int cavp_grad_guard_finish_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks,
+                                 const cavp_guard_partial* partials, cavp_guard_state* guard_device, const int32_t* gate_device,
+                                 void* stream);
+int cavp_optimizer_schedule_guarded_gated(cavp_opt_state* state_device, cavp_guard_state* guard_device, const float* loss0,
+                                          const float* loss1, const int32_t* gate_device, void* stream);
+int cavp_optimizer_step_guarded_gated(const cavp_opt_job* jobs_device, int32_t njobs, int32_t total_blocks, float momentum,
+                                      float eps, const cavp_opt_state* state_device, const cavp_guard_state* guard_device,
+                                      const int32_t* gate_device, void* stream);
+
 /* Step rollback (added to ABI 16): a skipped step also undoes what its forward wrote.  A device-resident table of byte ranges, two
  * launches whatever the number of ranges:
  *   cavp_rollback_save:    live -> shadow for every range without CAVP_ROLLBACK_SCRUB;

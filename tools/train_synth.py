@@ -13,7 +13,7 @@ shapes; the point is the plumbing and its throughput, not accuracy.
 usage: python tools/train_synth.py [--steps 20] [--batch 32] [--dtype bf16|f32] [--num-classes 2] [--from-waveform]
                                    [--contrast [--contrast-weight W]] [--pairs] [--graph [--augment [--resize] [--raw-audio]
                                    [--resident [--store-items N] [--clips T [--validate-every K]]]]
-                                   [--guard [--max-norm X] [--rollback]]] [--preview DIR]
+                                   [--guard [--max-norm X] [--rollback]] [--accumulate N]] [--preview DIR]
                                    [--seg-model DeepLabV3Plus|PVT [--device-droppath]]
 
 --contrast: the reference trainers' full objective, l_ce + W * l_ctr (trainer_cavp_vpo_mono.py:183-189), inside the native step:
@@ -57,6 +57,11 @@ returns the records written since (step, rate, both losses, gradient norm, coeff
 --augment, the frame augmentation, handed to both captures: a skipped step also undoes what its forward wrote, and the captures undo
 their own warm-up passes, so nothing is reloaded or reseeded behind them.  At the end the rollback's restore count is printed next to
 the guard's skipped count; the run fails if the two differ.
+
+--accumulate N (with --graph, one process, not with --rollback): a cavp_amd.accumulate.GradAccumulator on the recorded update - N
+replays of --batch frames per optimiser update, the arithmetic of N data-parallel ranks with local BatchNorm.  --steps and
+--total-iters then count WINDOWS (the loop replays --steps x N times), and so do the printed lines: with --guard one record per
+window (its losses are the window's means), otherwise the closing replay's loss.
 
 --device-droppath (with --seg-model PVT; an error otherwise): the backbone's DropPath masks are drawn on the device
 (model.use_device_drop_path(seed=1234 + rank), cavp_amd/droppath.py) - one launch per forward, inside the graph with --graph, where
@@ -107,6 +112,8 @@ def main():
     ap.add_argument("--max-norm", type=float, default=None, help="with --guard: clip the global gradient norm to this bound")
     ap.add_argument("--rollback", action="store_true", help="with --guard: a StepRollback over the model's BatchNorm state and every enabled "
                     "stage, so a skipped step also undoes its forward; the capture then leaves no trace and nothing is reseeded")
+    ap.add_argument("--accumulate", type=int, default=None, metavar="N", help="with --graph: N micro-batches of --batch frames per update "
+                    "(GradAccumulator); --steps and --total-iters count windows")
     ap.add_argument("--augment", action="store_true", help="with --graph: raw uint8 frames / masks through FrameAugment and LabelStage in the prologue")
     ap.add_argument("--resize", action="store_true", help="with --augment: the resize_flag variant (AVS scales, no jitter, resize to --hw)")
     ap.add_argument("--raw-audio", action="store_true", help="with --augment: 44.1 kHz int16 stereo PCM through WaveStage at the head of the prologue")
@@ -141,6 +148,8 @@ def main():
         ap.error("--max-norm needs --guard")
     if a.rollback and not a.guard:
         ap.error("--rollback needs --guard: the guard's skip word decides the restore")
+    if a.accumulate is not None and (not a.graph or a.rollback or a.accumulate < 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--accumulate N needs --graph, N >= 1, one process and no --rollback (a window spans several replays)")
     if a.graph and not a.pairs:
         ap.error("--graph needs --from-waveform --contrast --pairs")
     if a.device_droppath and a.seg_model != "PVT":
@@ -287,6 +296,10 @@ def main():
             from cavp_amd.optim import StepGuard
             guard = StepGuard(max_norm=a.max_norm, skip_nonfinite=True, history=64)
             opt.use_step_guard(guard)                           # before the captures: they record its four launches
+        acc = None
+        if a.accumulate is not None:
+            from cavp_amd.accumulate import GradAccumulator
+            acc = GradAccumulator(opt, a.accumulate)            # before the captures too: they record its gated launches
         start = {k: v.clone() for k, v in model.state_dict().items()}
 
         if a.augment:
@@ -359,7 +372,8 @@ def main():
         for ow in (False, True):
             rep = model.capture_train_step(s_image, s_audio, s_label, contrast=crit, label_shuffle=s_shuf,
                                            contrast_weight=a.contrast_weight, optimizer=opt, prologue=prologue_of(ow),
-                                           **({"rollback": rb} if rb is not None else {}))
+                                           **({"rollback": rb} if rb is not None else {}),
+                                           **({"accumulate": acc} if acc is not None else {}))
             replays.append((rep, model._last_losses))           # (each graph has its own static loss buffers)
         if rb is None:
             # the warm-up passes of the captures ran the pair builder, the sampler and the BatchNorm statistics for real: start over
@@ -408,7 +422,9 @@ def main():
             cv.check()
             return cv.results()
 
-    for it in range(a.steps):
+    N = a.accumulate or 1                                       # replays per update: the loop counts micro-steps, the prints windows
+    total = a.steps * N
+    for it in range(total):
         if validate is not None and it > 0 and it % a.validate_every == 0:
             all_, ms = validate()
             if rank == 0:
@@ -446,7 +462,7 @@ def main():
                 torch.cuda.synchronize()
                 t0 = time.time()
             if guard is not None:                               # the display_iter pattern: one read per 5 steps, every step shown
-                if it % 5 == 4 or it == a.steps - 1:
+                if it % 5 == 4 or it == total - 1:
                     rec = guard.read()
                     if first is None and len(rec["t"]):
                         first = float(rec["l_ce"][0] + a.contrast_weight * rec["l_ctr"][0])
@@ -459,9 +475,9 @@ def main():
                 continue
             if first is None:
                 first = float(loss.item())
-            if rank == 0 and (it % 5 == 0 or it == a.steps - 1):
+            if rank == 0 and (it + 1) % N == 0 and ((it // N) % 5 == 0 or it == total - 1):
                 terms = "  (CE {:.4f}, contrast {:.4f})".format(*(float(t.item()) for t in graph_terms))
-                print(f"iter {it:4d}  lr {float(opt.last_lr().item()):.3e}  loss {float(loss.item()):.4f}{terms}", flush=True)
+                print(f"iter {it // N:4d}  lr {float(opt.last_lr().item()):.3e}  loss {float(loss.item()):.4f}{terms}", flush=True)
             continue
         image, label = image.to(dev), label.to(dev)
         built = None
@@ -497,10 +513,14 @@ def main():
             terms = "  (CE {:.4f}, contrast {:.4f})".format(*(float(t.item()) for t in model._last_losses)) if crit is not None else ""
             print(f"iter {it:4d}  lr {sched(it):.3e}  loss {float(loss.item()):.4f}{terms}", flush=True)
     torch.cuda.synchronize()
-    if rank == 0 and t0 is not None and a.steps > 2:
-        dt = (time.time() - t0) / (a.steps - 2)
+    if rank == 0 and t0 is not None and total > 2:
+        dt = (time.time() - t0) / (total - 2)
         print(f"{B * world / dt:.1f} frames/s over {world} GPU(s) ({dt * 1e3:.1f} ms/step incl. host-side input generation, "
               f"{'one graph replay' if a.graph else 'eager launches, optimiser step'})")
+    if rank == 0 and a.accumulate is not None:
+        rd = acc.read()
+        print(f"accumulate: {rd['windows']} windows of {N} replays ({rd['micro_total']} replays, effective batch {B * N}), "
+              f"t = {opt.iteration()}, accumulator {acc.nbytes / 1e6:.1f} MB")
     if rb is not None:
         stats, skipped = rb.stats(), int(guard.last()["skipped_total"].item())
         if rank == 0:
