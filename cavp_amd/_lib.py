@@ -181,6 +181,9 @@ PROTOTYPES = {
     "cavp_space_to_depth": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_row_scale_add": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "cavp_drop_path_draw": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),   # DropPath masks on the device (added to ABI 16)
+    # ---- ResNet-18 audio encoder: fused stem + pool, global max (added to ABI 16) ----
+    "cavp_audio_stem_pool": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "cavp_global_maxpool_nhwc": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     # ---- validation metrics ----
     "cavp_seg_confusion_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp]),
     "cavp_mask_iou_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp]),

@@ -226,15 +226,60 @@ class VGG(_Container):
                                         nn.ReLU(True), nn.Linear(4096, out_plane), nn.ReLU(True))
 
 
+class BasicBlock(_Container):
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride, downsample):
+        super().__init__()
+        self.conv1, self.bn1 = _conv(inplanes, planes, 3, stride, 1), _bn(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2, self.bn2 = _conv(planes, planes, 3, 1, 1), _bn(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+
+class ResNet18Audio(_Container):
+    """torchvision's resnet18 as the reference rewires it (audio_network.py:18-25): conv1 takes `in_plane` channels, `avgpool` is a
+    global MAX pool and `fc` maps 512 -> out_plane with no activation behind it.  Attribute tree and state_dict keys are torchvision's.
+    Initialisation is torchvision's too (Kaiming-normal fan_out convs, BatchNorm 1 / 0, no zero-init residual); ImageNet weights are
+    never fetched - they arrive, like any others, through load_state_dict."""
+    WIDTHS = (64, 128, 256, 512)
+
+    def __init__(self, out_plane, in_plane=1):
+        super().__init__()
+        self.in_plane = in_plane
+        self.conv1, self.bn1 = _conv(in_plane, 64, 7, 2, 3), _bn(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        inplanes = 64
+        for li, planes in enumerate(self.WIDTHS):
+            stride = 1 if li == 0 else 2
+            ds = nn.Sequential(_conv(inplanes, planes, 1, stride), _bn(planes)) if (stride != 1 or inplanes != planes) else None
+            setattr(self, f"layer{li + 1}", nn.Sequential(BasicBlock(inplanes, planes, stride, ds), BasicBlock(planes, planes, 1, None)))
+            inplanes = planes
+        self.avgpool = nn.AdaptiveMaxPool2d((1, 1))
+        self.fc = nn.Linear(512, out_plane)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+
+
+_AUDIO18_TRAINING = "training of the ResNet-18 audio encoder is not built yet; eval only"
+
+
 class AudioModel(_Container):
     def __init__(self, backbone, pretrain_path, out_plane, num_classes=2, in_plane=1):
         super().__init__()
-        if backbone != "vgg":
-            raise ValueError("HIP path implements the VGGish audio encoder (audio_backbone='vgg'); the torchvision "
-                             "ResNet-18 branch is out of scope (SURVEY.md §2.1 row 5)")
-        self.backbone = VGG(out_plane)
-        if pretrain_path is not None:
-            self.load_audio_model(pretrain_path)
+        if backbone in ("18", 18):
+            # (pretrain_path is ignored, as in the reference: audio_network.py:18-25 never reads it on this branch)
+            self.backbone = ResNet18Audio(out_plane, in_plane)
+        elif backbone != "vgg":
+            raise ValueError("HIP path implements the VGGish (audio_backbone='vgg') and the ResNet-18 (audio_backbone='18') audio "
+                             f"encoders; got {backbone!r}")
+        else:
+            self.backbone = VGG(out_plane)
+            if pretrain_path is not None:
+                self.load_audio_model(pretrain_path)
         self.cls_head = nn.Linear(out_plane, num_classes)  # unused on the path, present in checkpoints
 
     def load_audio_model(self, path_):
@@ -409,13 +454,16 @@ class CAVP(nn.Module):
         P["head0"] = self._pack_conv(up.last_conv[0], up.last_conv[1])
         P["head1"] = self._pack_conv(up.last_conv[3], up.last_conv[4])
         P["cls"] = self._pack_conv(up.classifier)
-        vgg = self.audio_backbone.backbone
-        convs = [m for m in vgg.features if isinstance(m, nn.Conv2d)]
-        P["a.conv0"] = self._pack_conv(convs[0], raw=True)
-        for i, cv in enumerate(convs[1:], 1):
-            P[f"a.conv{i}"] = self._pack_conv(cv)
-        for i, j in enumerate((0, 2, 4)):
-            P[f"a.fc{i}"] = self._pack_conv(vgg.embeddings[j])
+        if self._audio18():
+            self._pack_audio18(P)
+        else:
+            vgg = self.audio_backbone.backbone
+            convs = [m for m in vgg.features if isinstance(m, nn.Conv2d)]
+            P["a.conv0"] = self._pack_conv(convs[0], raw=True)
+            for i, cv in enumerate(convs[1:], 1):
+                P[f"a.conv{i}"] = self._pack_conv(cv)
+            for i, j in enumerate((0, 2, 4)):
+                P[f"a.fc{i}"] = self._pack_conv(vgg.embeddings[j])
         P["proj.fc1"] = self._pack_conv(self.visual_projector.fc1)
         P["proj.fc2"] = self._pack_conv(self.visual_projector.fc2)
         ca, blk = self.cross_att, self.cross_att.blocks[0]
@@ -426,6 +474,29 @@ class CAVP(nn.Module):
         P["ca.fc1"] = self._pack_conv(blk.mlp.fc1)
         P["ca.fc2"] = self._pack_conv(blk.mlp.fc2)
         return P
+
+    def _audio18(self) -> bool:
+        return isinstance(self.audio_backbone.backbone, ResNet18Audio)
+
+    def _fence_audio18(self, what: str) -> None:
+        """The ResNet-18 audio encoder has the eval forward only: every training entry point calls this first - before a kernel is
+        queued, before the gradient arena exists or is zeroed - so parameters and BatchNorm buffers are as they were.  (Called as
+        CAVP._fence_audio18(self, ...) where the entry point's own argument checks are reachable without a model: an object with no
+        audio encoder has nothing to fence.)"""
+        if isinstance(getattr(getattr(self, "audio_backbone", None), "backbone", None), ResNet18Audio):
+            raise CavpError(f"CAVP.{what}: {_AUDIO18_TRAINING} (audio_backbone='18')")
+
+    def _pack_audio18(self, P):
+        rn = self.audio_backbone.backbone
+        P["a18.stem"] = self._pack_conv(rn.conv1, rn.bn1, raw=True)   # f32 OIHW, as cavp_audio_stem_pool reads it
+        for li in range(4):
+            for bi, blk in enumerate(getattr(rn, f"layer{li + 1}")):
+                key = f"a18.l{li + 1}.{bi}"
+                P[key + ".c1"] = self._pack_conv(blk.conv1, blk.bn1)
+                P[key + ".c2"] = self._pack_conv(blk.conv2, blk.bn2)
+                if blk.downsample is not None:
+                    P[key + ".ds"] = self._pack_conv(blk.downsample[0], blk.downsample[1])
+        P["a18.fc"] = self._pack_conv(rn.fc)
 
     def packed(self) -> Dict[str, _ConvP]:
         sig = self._signature()
@@ -501,8 +572,43 @@ class CAVP(nn.Module):
         self._conv(f1, P["reduce"], out=fea_v[..., co:], act=ACT_RELU)
         return fea_v, aspp
 
-    def _audio_hip(self, audio, P):
-        """AudioModel.forward -> VGG.forward (vgg.py:17-23): fea_a [B, 304] (>= 0)."""
+    def _audio18_hip(self, audio, P, taps: Optional[dict] = None):
+        """AudioModel.forward -> torchvision ResNet._forward_impl with the reference's rewiring (audio_network.py:18-25):
+        [N, in_plane, T, F] f32 -> fea_a [N, latent], no activation behind fc (entries of either sign).  22 launches: the fused stem,
+        19 igemm convs (folded BatchNorm, ReLU and the residual add in their epilogues), the global max, fc."""
+        rn = self.audio_backbone.backbone
+        dt, dev = self.compute_dtype, audio.device
+        if audio.dim() != 4 or audio.shape[1] != rn.in_plane:
+            raise CavpError(f"ResNet-18 audio encoder was built with in_plane={rn.in_plane}: expected [N, {rn.in_plane}, T, F] log-mel "
+                            f"input, got {tuple(audio.shape)}")
+        if audio.dtype != torch.float32:
+            raise CavpError("audio must be float32 (it is converted on the fly by the stem kernel)")
+        N, _, H, W = audio.shape
+        hs, ws = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        p0 = P["a18.stem"]
+        x = torch.empty((N, (hs - 1) // 2 + 1, (ws - 1) // 2 + 1, 64), dtype=dt, device=dev)
+        ops.audio_stem_pool(audio.contiguous(), p0.w, p0.scale, p0.shift, x)
+        if taps is not None:
+            taps["a18.stem"] = x.permute(0, 3, 1, 2)
+        for li in range(4):
+            for bi in range(2):
+                key = f"a18.l{li + 1}.{bi}"
+                o = self._conv(x, P[key + ".c1"], act=ACT_RELU)
+                res = self._conv(x, P[key + ".ds"]) if (key + ".ds") in P else x
+                x = self._conv(o, P[key + ".c2"], act=ACT_RELU, residual=res)
+            if taps is not None:
+                taps[f"a18.layer{li + 1}"] = x.permute(0, 3, 1, 2)
+        pooled = ops.global_maxpool(x, torch.empty((N, x.shape[-1]), dtype=dt, device=dev))
+        if taps is not None:
+            taps["a18.pool"] = pooled
+        return self._lin(pooled, P["a18.fc"])
+
+    def _audio_hip(self, audio, P, taps: Optional[dict] = None):
+        """AudioModel.forward.  VGG.forward (vgg.py:17-23): fea_a [B, 304] (>= 0: it ends in a ReLU); the ResNet-18 encoder
+        (_audio18_hip) ends in a plain Linear, so its features have either sign.  Nothing downstream relies on the sign: the fusion
+        block embeds fea_a with a Linear and a LayerNorm before it forms the key / value token (_fusion_hip, csrc/attn_rank1.hip)."""
+        if self._audio18():
+            return self._audio18_hip(audio, P, taps)
         dt, dev = self.compute_dtype, audio.device
         B, cin, H, W = audio.shape
         if cin != 1:
@@ -624,7 +730,7 @@ class CAVP(nn.Module):
             ev0.record(main)
             side.wait_event(ev0)
             with torch.cuda.stream(side), ops.workspace_slot(1):
-                fea_a = self._audio_hip(audio, P)
+                fea_a = self._audio_hip(audio, P, taps)
                 ev1 = torch.cuda.Event()
                 ev1.record(side)
         if self.seg_model == "PVT":
@@ -634,7 +740,7 @@ class CAVP(nn.Module):
             feats = self._backbone_hip(image, P)
         fea_v, aspp = self._forward_feature_hip(feats, P)
         if side is None:
-            fea_a = self._audio_hip(audio, P)
+            fea_a = self._audio_hip(audio, P, taps)
         else:
             torch.cuda.current_stream().wait_event(ev1)
         if shuffle is not None:   # forward_audio (cavp_model.py:156-173): B clips -> features | shuffled features
@@ -729,6 +835,7 @@ class CAVP(nn.Module):
         with ow_flag the SoundBank is updated from the image labels.  With gradients enabled the encoder and the gather run on a
         training tape of their own (CAVPStageFunction); inside forward_train(audio_func=True) they are part of the model's pass."""
         if self._stage_on_tape((self.audio_backbone,), audio):
+            self._fence_audio18("forward_audio on a training tape")
             return self._stage_apply("audio", (shuffle_info, ow_flag), (self.audio_backbone,), audio)
         with torch.no_grad():
             a = audio.contiguous()
@@ -779,6 +886,7 @@ class CAVP(nn.Module):
         want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if not bn_train and not want_grad:
             return self._forward_hip(image, audio, duplicate_visual=True, shuffle=shuffle)   # frozen-BN, forward only
+        self._fence_audio18("forward_train with gradients or batch-statistics BatchNorm")
         if not image.is_cuda:
             raise CavpError("CAVP (MI355X path) needs inputs on a HIP device: there is no CPU fallback")
         from .train import CAVPTrainFunction
@@ -823,6 +931,8 @@ class CAVP(nn.Module):
         (`out = model(...)`, torch loss, `loss.backward()`, torch optimisers) at graph speed.  The returned tensors are static
         buffers, overwritten by the next forward.  Changing the compute dtype, the set of trainable parameters or train / eval
         mode of the BatchNorm layers needs a fresh `enable_graphed_autograd()`."""
+        if on:
+            self._fence_audio18("enable_graphed_autograd")
         self.__dict__["_graphed_autograd"] = [] if on else None
 
     def use_device_drop_path(self, seed: Optional[int] = 0):
@@ -895,6 +1005,7 @@ class CAVP(nn.Module):
         from . import train_ops as T
         from .train import (TrainPass, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world,
                             run_train_forward)
+        self._fence_audio18("train_step")
         if not image.is_cuda:
             raise CavpError("CAVP (MI355X path) needs inputs on a HIP device: there is no CPU fallback")
         arena = self.grad_arena(image.device)
@@ -998,6 +1109,7 @@ class CAVP(nn.Module):
         schedule's lengths count windows).  After a replay `p.grad` holds that micro-batch's gradient, after a window's last replay the
         window's sum; the returned loss is the micro-batch's.  The warm-up passes and the capture leave the accumulator and its k
         alone.  Not with `rollback=` and not with collectives on."""
+        CAVP._fence_audio18(self, "capture_train_step")   # first: before the argument checks, long before the first pass
         from .accumulate import check_capture
         from .train import _no_gc_during_capture, allreduce_arena_early, allreduce_arena_late, collectives_on, dist_world
         micro_steps = check_capture(accumulate, optimizer, rollback, collectives_on())

@@ -243,6 +243,43 @@ def global_avgpool(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def global_maxpool(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out [N, C] (x's dtype, contiguous) = max over H x W of the NHWC view x: nn.AdaptiveMaxPool2d((1, 1))."""
+    _need_gpu(x, out)
+    n, h, w, c, ld = _nhwc(x)
+    if out.dtype != x.dtype or tuple(out.shape) != (n, c) or not out.is_contiguous():
+        raise _lib.CavpError("global_maxpool: out must be contiguous [N, C] of the input's dtype")
+    st = _lib.load().cavp_global_maxpool_nhwc(dtype_code(x.dtype), _ptr(x), _ptr(out), n, h * w, c, ld,
+                                              C.c_void_p(_stream()))
+    _lib.check(st, "cavp_global_maxpool_nhwc")
+    return out
+
+
+def audio_stem_pool(x_nchw: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                    out: torch.Tensor) -> torch.Tensor:
+    """ResNet-18 audio stem in one launch: conv 7x7 / 2 / 3 (no bias) -> * scale + shift (folded BatchNorm) -> ReLU -> max pool 3 / 2 / 1.
+    x f32 NCHW [N, Cin <= 2, H, W], w f32 OIHW [64, Cin, 7, 7], out dense NHWC [N, Hp, Wp, 64] (f32 or bf16)."""
+    _need_gpu(x_nchw, w_oihw, scale, shift, out)
+    if x_nchw.dim() != 4 or x_nchw.dtype != torch.float32 or w_oihw.dtype != torch.float32 or not x_nchw.is_contiguous() \
+            or not w_oihw.is_contiguous():
+        raise _lib.CavpError("audio_stem_pool: x and w must be contiguous f32 (NCHW / OIHW)")
+    n, cin, h, w = x_nchw.shape
+    if cin not in (1, 2) or tuple(w_oihw.shape) != (64, cin, 7, 7):
+        raise _lib.CavpError(f"audio_stem_pool: 1 or 2 input channels and a [64, Cin, 7, 7] weight; got x {tuple(x_nchw.shape)}, "
+                             f"w {tuple(w_oihw.shape)}")
+    for name, v in (("scale", scale), ("shift", shift)):
+        if v.dtype != torch.float32 or v.numel() != 64 or not v.is_contiguous():
+            raise _lib.CavpError(f"audio_stem_pool: {name} must be a contiguous f32 [64]")
+    no, ho, wo, co, ldy = _nhwc(out)
+    hs, ws = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    if (no, ho, wo, co) != (n, (hs - 1) // 2 + 1, (ws - 1) // 2 + 1, 64) or ldy != 64 or not out.is_contiguous():
+        raise _lib.CavpError("audio_stem_pool: bad output view")
+    st = _lib.load().cavp_audio_stem_pool(dtype_code(out.dtype), _ptr(x_nchw), _ptr(w_oihw), _ptr(scale), _ptr(shift), _ptr(out),
+                                          n, cin, h, w, C.c_void_p(_stream()))
+    _lib.check(st, "cavp_audio_stem_pool")
+    return out
+
+
 def bilinear(x: torch.Tensor, out: torch.Tensor, align_corners: bool) -> torch.Tensor:
     _need_gpu(x, out)
     n, hi, wi, c, ldx = _nhwc(x)

@@ -755,6 +755,18 @@ int cavp_row_scale_add(int32_t dtype, const void* x, const void* branch, const f
  * (CAVP_ERR_BAD_ARG), n * B <= 2^20 (CAVP_ERR_UNSUPPORTED). */
 int cavp_drop_path_draw(int64_t* state, const float* keep, const float* inv_keep, int32_t n, int32_t B, float* out, void* stream);
 
+/* ---- ResNet-18 audio encoder (two entry points added to ABI 16; nothing else changed): the eval forward of the reference's non-VGG
+ * AudioModel (audio_network.py:18-25: torchvision resnet18, conv1 in_plane -> 64, avgpool = AdaptiveMaxPool2d((1, 1)), fc 512 -> out).
+ * Its sixteen 3x3 and three 1x1 convs run through cavp_conv2d_nhwc; csrc/audio_resnet.hip holds the two launches below. ----
+ * conv1 (7x7, stride 2, pad 3, no bias) + folded bn1 (scale / shift, f32 [64]) + ReLU + MaxPool2d(3, 2, 1) in ONE launch: the stem map
+ * [N][Hs][Ws][64], Hs = (H - 1) / 2 + 1, stays in LDS.  x f32 NCHW [N][Cin][H][W], Cin = 1 or 2 (else CAVP_ERR_UNSUPPORTED); w f32 OIHW
+ * [64][Cin][7][7]; y dense NHWC [N][Hp][Wp][64] of dtype (f32 accumulation), Hp = (Hs - 1) / 2 + 1, 16-byte aligned.  Any H, W >= 1. */
+int cavp_audio_stem_pool(int32_t dtype, const float* x_nchw, const float* w_oihw, const float* scale, const float* shift,
+                         void* y_nhwc, int32_t N, int32_t Cin, int32_t H, int32_t W, void* stream);
+/* x.amax over HW for NHWC x [N][HW][C] with row stride ldx; y [N][C] of the SAME dtype (a maximum needs no wider type), dense.  HW >= 1;
+ * the running maximum starts at -inf.  N <= 65535. */
+int cavp_global_maxpool_nhwc(int32_t dtype, const void* x, void* y, int32_t N, int32_t HW, int32_t C, int32_t ldx, void* stream);
+
 /* ---- validation metrics (ABI 13; utils/eval_utils.py MIoU / ForegroundDetect, utils/avsbench_utils.py mask_iou / Eval_Fmeasure) ----
  * Integer counts only, accumulated with integer atomics: results are independent of arrival order.  The float finalisation stays
  * on the host side (cavp_amd/metrics.py), in the reference's expressions.  None of these clears its output (cavp_zero_bytes). */
