@@ -134,6 +134,10 @@ PROTOTYPES = {
                                      _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "cavp_bn_act_bwd_apply_acc": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32,
                                          _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # tile combine inside the apply pass, forward and backward (added to ABI 16)
+    "cavp_bn_tiles_scale_shift_act": (_i32, [_i32, _vp, _vp, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "cavp_bn_tiles_bwd_apply": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     "cavp_act_bwd": (_i32, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cavp_add": (_i32, [_i32, _vp, _vp, _vp, _i64, _vp]),
     "cavp_colsum": (_i32, [_i32, _vp, _i64, _i32, _i32, _vp, _vp]),

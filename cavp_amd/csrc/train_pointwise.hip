@@ -315,6 +315,57 @@ __device__ __forceinline__ void chan_combine(float& n, float& mean, float& m2, f
   m2 += m2b + dlt * dlt * (n * nb / nt);
   n = nt;
 }
+// One step of the butterfly that merges the lanes' partial moments: `self` is the lane's own value, (nb, mb, m2b) its partner's.
+// Lane 0 ends with a fixed tree in which the lower lane of every pair is `self`.
+__device__ __forceinline__ void chan_combine_sym(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
+  const float nt = n + nb;
+  if (nt > 0.f) {
+    const float dlt = mb - mean;
+    const float nm = mean + dlt * (nb / nt);
+    m2 = m2 + m2b + dlt * dlt * (n * nb / nt);
+    mean = nm;
+    n = nt;
+  }
+}
+// rows of tile t (the last tile may be ragged)
+__device__ __forceinline__ float tile_rows_f(long long M, int t, int rows_per_tile) {
+  long long nb = M - (long long)t * rows_per_tile;
+  if (nb > rows_per_tile) nb = rows_per_tile;
+  return (float)nb;
+}
+// The one-wave combine of a channel's tile moments, shared by bn_finalize_tiles_kernel and the fused apply kernel
+// (bn_tiles_scale_shift_act_kernel).  THE SUMMATION ORDER IS THE CONTRACT: virtual lane L (0..63) folds tiles L, L + 64, ... in
+// ascending order with chan_combine, then chan_combine_sym merges lanes L and L + o for o = 32, 16, 8, 4, 2, 1 (L < o is `self`)
+// and lane 0's value is the result.  lane_chain_step is the chain, wave_butterfly the tree on a real wave.
+__device__ __forceinline__ void lane_chain_step(float& n, float& mean, float& m2, long long M, int t, int rows_per_tile, float2 q) {
+  chan_combine(n, mean, m2, tile_rows_f(M, t, rows_per_tile), q.x, q.y);
+}
+__device__ __forceinline__ void wave_butterfly(float& n, float& mean, float& m2) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float nb = __shfl_xor(n, o, 64), mb = __shfl_xor(mean, o, 64), m2b = __shfl_xor(m2, o, 64);
+    chan_combine_sym(n, mean, m2, nb, mb, m2b);
+  }
+}
+// batch statistics -> folded coefficients, saved statistics and the running-statistics update of one channel
+__device__ __forceinline__ void bn_channel_finish(float mean, float m2, long long M, int c, const float* gamma, const float* beta, float eps,
+                                                  float momentum, float* rmean, float* rvar, float& sc, float& sh, float& rstd, bool write,
+                                                  float* scale, float* shift, float* mean_out, float* rstd_out) {
+  const float var = m2 / (float)M;
+  rstd = 1.f / sqrtf(var + eps);
+  sc = gamma[c] * rstd;
+  sh = beta[c] - mean * sc;
+  if (!write) return;
+  scale[c] = sc;
+  shift[c] = sh;
+  mean_out[c] = mean;
+  rstd_out[c] = rstd;
+  if (rmean) {
+    const float unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.f;
+    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+    rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * unbias;
+  }
+}
 __global__ __launch_bounds__(256) void bn_finalize_tiles_kernel(const float* __restrict__ ts, int tiles, int rows_per_tile,
                                                                 long long M, const float* gamma, const float* beta,
                                                                 float eps, float momentum, float* rmean, float* rvar,
@@ -335,42 +386,16 @@ __global__ __launch_bounds__(256) void bn_finalize_tiles_kernel(const float* __r
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int t = t0 + 64 * u;
-      if (t < tiles) {
-        long long nb = M - (long long)t * rows_per_tile;
-        if (nb > rows_per_tile) nb = rows_per_tile;
-        chan_combine(n, mean, m2, (float)nb, q[u].x, q[u].y);
-      }
+      if (t < tiles) lane_chain_step(n, mean, m2, M, t, rows_per_tile, q[u]);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float nb = __shfl_xor(n, o, 64), mb = __shfl_xor(mean, o, 64), m2b = __shfl_xor(m2, o, 64);
-    // symmetric combine so every lane ends with the same value
-    const float nt = n + nb;
-    if (nt > 0.f) {
-      const float dlt = mb - mean;
-      const float nm = mean + dlt * (nb / nt);
-      m2 = m2 + m2b + dlt * dlt * (n * nb / nt);
-      mean = nm;
-      n = nt;
-    }
-  }
+  wave_butterfly(n, mean, m2);
   if (lane == 0 && moments) {   // SyncBatchNorm: this rank's (mean, M2), combined across ranks by a second call
     moments[2 * c] = mean;
     moments[2 * c + 1] = m2;
   } else if (lane == 0) {
-    const float var = m2 / (float)M;
-    const float rstd = 1.f / sqrtf(var + eps);
-    const float sc = gamma[c] * rstd;
-    scale[c] = sc;
-    shift[c] = beta[c] - mean * sc;
-    mean_out[c] = mean;
-    rstd_out[c] = rstd;
-    if (rmean) {
-      const float unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.f;
-      rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-      rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * unbias;
-    }
+    float sc, sh, rstd;
+    bn_channel_finish(mean, m2, M, c, gamma, beta, eps, momentum, rmean, rvar, sc, sh, rstd, true, scale, shift, mean_out, rstd_out);
   }
 }
 
@@ -506,6 +531,17 @@ __global__ __launch_bounds__(256) void scale_shift_act_flat_kernel(const T* __re
   }
 }
 
+// dz = a_c * g + b_c * z + c_c (see bn_bwd_apply_kernel): the per-channel coefficients and the per-element expression, shared by
+// the apply kernels so that the fused one (bn_tiles_bwd_apply_kernel) rounds exactly as they do
+__device__ __forceinline__ void bn_bwd_coeffs(float gm, float rs, float mu, float sg, float sgz, float inv_m, float& ca, float& cb,
+                                              float& cc) {
+  const float a = gm * rs;
+  ca = a;
+  cb = -a * rs * sgz * inv_m;
+  cc = -a * sg * inv_m - cb * mu;
+}
+__device__ __forceinline__ float bn_bwd_dz(float ca, float g, float cb, float z, float cc) { return ca * g + cb * z + cc; }
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const T* __restrict__ dy, const T* __restrict__ y,
                                                                 const T* __restrict__ z, const float* __restrict__ mean,
@@ -531,12 +567,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const T* __restr
       VecT<float>::load(sum_gz + c + q, sgz + q); VecT<float>::load(mean + c + q, mu + q);
     }
 #pragma unroll
-    for (int e = 0; e < VE; ++e) {
-      const float a = gm[e] * rs[e];
-      ca[e] = a;
-      cb[e] = -a * rs[e] * sgz[e] * inv_m;
-      cc[e] = -a * sg[e] * inv_m - cb[e] * mu[e];
-    }
+    for (int e = 0; e < VE; ++e) bn_bwd_coeffs(gm[e], rs[e], mu[e], sg[e], sgz[e], inv_m, ca[e], cb[e], cc[e]);
     // the sums ARE the affine gradients (dbeta = sum g, dgamma = sum g * zhat): when they arrive in scratch (summed by the
     // data-gradient launch's epilogue, cavp_conv2d_nhwc_bnbwd) one thread per channel vector adds them to the parameter gradients
     if (acc_g && blockIdx.x == 0 && rsub == 0) {
@@ -568,7 +599,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const T* __restr
 #pragma unroll
     for (int e = 0; e < VE; ++e) {
       g[e] = a[e] * act_grad_from_out(yy[e], act);
-      o[e] = ca[e] * g[e] + cb[e] * zz[e] + cc[e];
+      o[e] = bn_bwd_dz(ca[e], g[e], cb[e], zz[e], cc[e]);
     }
     VecT<T>::store(dz + r * ld_dz + c, o);
     if (g_out) VecT<T>::store(g_out + r * ld_g + c, g);
@@ -594,10 +625,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   float ca[VE], cb[VE], cc[VE];
 #pragma unroll
   for (int e = 0; e < VE; ++e) {
-    const float rs = rstd[c + e], a = gamma[c + e] * rs;
-    ca[e] = a;
-    cb[e] = -a * rs * sum_gz[c + e] * inv_m;
-    cc[e] = -a * sum_g[c + e] * inv_m - cb[e] * mean[c + e];
+    bn_bwd_coeffs(gamma[c + e], rstd[c + e], mean[c + e], sum_g[c + e], sum_gz[c + e], inv_m, ca[e], cb[e], cc[e]);
     if (acc_g && blockIdx.x == 0 && rl == 0) { acc_g[c + e] += sum_g[c + e]; acc_gz[c + e] += sum_gz[c + e]; }   // (see the flat kernel)
   }
   const bool from_z = y == nullptr;   // activation mask re-derived from z (layers without a residual): y is not read
@@ -623,7 +651,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
     for (int e = 0; e < VE; ++e) {
       g[e] = a[e] * act_grad_from_out(yy[e], act);
-      o[e] = ca[e] * g[e] + cb[e] * zz[e] + cc[e];
+      o[e] = bn_bwd_dz(ca[e], g[e], cb[e], zz[e], cc[e]);
     }
     VecT<T>::store(dz + r * ld_dz + c, o);
     if (g_out) VecT<T>::store(g_out + r * ld_g + c, g);
@@ -1729,6 +1757,16 @@ extern "C" int cavp_scale_shift_act(int32_t dtype, const void* x, const float* s
 // Sum the per-tile (sum g, sum g * zhat) pairs a data-gradient launch wrote (cavp_conv2d_nhwc_bnbwd) over the tiles: 256 threads =
 // 16 channels x 16 tile lanes (a tile row of 16 channels is 128 contiguous bytes), lane sums in ascending tile order, then a fixed
 // tree over the 16 lanes through LDS.  Adds into sum_g / sum_gz (the BatchNorm's affine-gradient buffers).
+// The two halves of that sum, shared with the fused apply kernel (bn_tiles_bwd_apply_kernel).  THE SUMMATION ORDER IS THE CONTRACT:
+// tile lane tl (0..15) adds tiles tl, tl + 16, ... in ascending order (bwd_lane_add per tile; how many loads are in flight is the
+// caller's business), then the 16 lane sums are added in lane order starting from 0 (bwd_sum16).
+__device__ __forceinline__ void bwd_lane_add(float& a0, float& a1, float2 q) { a0 += q.x; a1 += q.y; }
+template <int LD>
+__device__ __forceinline__ void bwd_sum16(const float2 (*red)[LD], int ch, float& s0, float& s1) {
+  s0 = 0.f; s1 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) { s0 += red[k][ch].x; s1 += red[k][ch].y; }
+}
 __global__ __launch_bounds__(256) void bn_bwd_sum_tiles_kernel(const float* __restrict__ part, int tiles, int C, float* __restrict__ sum_g,
                                                                float* __restrict__ sum_gz) {
   __shared__ float2 red[16][17];
@@ -1742,19 +1780,15 @@ __global__ __launch_bounds__(256) void bn_bwd_sum_tiles_kernel(const float* __re
 #pragma unroll
       for (int u = 0; u < 8; ++u) q[u] = *(const float2*)(part + ((size_t)(t + 16 * u) * C + c) * 2);
 #pragma unroll
-      for (int u = 0; u < 8; ++u) { a0 += q[u].x; a1 += q[u].y; }
+      for (int u = 0; u < 8; ++u) bwd_lane_add(a0, a1, q[u]);
     }
-    for (; t < tiles; t += 16) {
-      const float2 q = *(const float2*)(part + ((size_t)t * C + c) * 2);
-      a0 += q.x; a1 += q.y;
-    }
+    for (; t < tiles; t += 16) bwd_lane_add(a0, a1, *(const float2*)(part + ((size_t)t * C + c) * 2));
   }
   red[tl][ch] = make_float2(a0, a1);
   __syncthreads();
   if (tl == 0 && c < C) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { s0 += red[k][ch].x; s1 += red[k][ch].y; }
+    float s0, s1;
+    bwd_sum16<17>(red, ch, s0, s1);
     sum_g[c] += s0;
     sum_gz[c] += s1;
   }
@@ -1763,6 +1797,246 @@ __global__ __launch_bounds__(256) void bn_bwd_sum_tiles_kernel(const float* __re
 extern "C" int cavp_bn_bwd_sum_tiles(const float* partials, int32_t tiles, int32_t C, float* sum_g, float* sum_gz, void* stream) {
   if (!partials || !sum_g || !sum_gz || tiles <= 0 || C <= 0) return CAVP_ERR_BAD_ARG;
   bn_bwd_sum_tiles_kernel<<<(C + 15) / 16, 256, 0, (hipStream_t)stream>>>(partials, tiles, C, sum_g, sum_gz);
+  CHECK_LAUNCH();
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Tile combine INSIDE the apply pass (launches with few tiles: the 7x7 .. 28x28 maps).  A workgroup owns a slice of BNF_SW = 64
+// channels and a block of rows.  It issues its first activation loads, then all table loads of its slice, combines the slice's
+// tiles redundantly (every workgroup of a slice computes the same 64 results, in the order bn_finalize_tiles_kernel /
+// bn_bwd_sum_tiles_kernel use), keeps the coefficients in LDS and runs the row loop.  The row-block-0 workgroup of a slice is
+// the only one that writes per-channel results; no workgroup reads what another one of the same launch wrote.
+// Thread mapping of the combine: 256 threads = 64 channels (fast: a tile row of the slice is 512 contiguous bytes) x 4 waves.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int BNF_SW = 64;
+
+// Forward.  Wave w of the workgroup holds the virtual lanes L = 4 k + w (k = 0..15) of every channel of the slice, so the tree
+// steps o = 32, 16, 8, 4 pair values of the same thread (k with k + o / 4) and only o = 2, 1 cross the waves through LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_tiles_scale_shift_act_kernel(const T* __restrict__ x, const float* __restrict__ ts, int tiles,
+                                                                       int rows_per_tile, long long M, const float* __restrict__ gamma,
+                                                                       const float* __restrict__ beta, float eps, float momentum,
+                                                                       float* rmean, float* rvar, float* scale, float* shift,
+                                                                       float* mean_out, float* rstd_out, const T* __restrict__ res,
+                                                                       T* __restrict__ y, int C, int rows_per_block, int ldx, int ldr,
+                                                                       int ldy, int act) {
+  constexpr int VE = VecT<T>::VE, CVS = BNF_SW / VE, RPT = 256 / CVS;
+  __shared__ float part[4][3][BNF_SW];
+  __shared__ float coef[2][BNF_SW];
+  const int c_base = blockIdx.y * BNF_SW;
+  const int cv = threadIdx.x % CVS, rsub = threadIdx.x / CVS;
+  const int c = c_base + cv * VE;
+  const bool col_ok = c < C;
+  const long long r0 = (long long)blockIdx.x * rows_per_block;
+  long long r1 = r0 + rows_per_block;
+  if (r1 > M) r1 = M;
+  long long r = r0 + rsub;
+  // first activation loads, ahead of the table loads
+  float v0[VE], q0[VE];
+  const bool have0 = col_ok && r < r1;
+  if (have0) {
+    VecT<T>::load(x + r * ldx + c, v0);
+    if (res) VecT<T>::load(res + r * ldr + c, q0);
+  }
+  const int ch = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int cc = c_base + ch;
+  const bool ch_ok = cc < C;
+  float n[16], mean[16], m2[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) n[k] = mean[k] = m2[k] = 0.f;
+  for (int tb = 0; tb < tiles; tb += 64) {   // 16 loads in flight per thread
+    float2 q[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int t = tb + 4 * k + w;
+      q[k] = (ch_ok && t < tiles) ? *(const float2*)(ts + ((size_t)t * C + cc) * 2) : make_float2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int t = tb + 4 * k + w;
+      if (ch_ok && t < tiles) lane_chain_step(n[k], mean[k], m2[k], M, t, rows_per_tile, q[k]);
+    }
+  }
+#pragma unroll
+  for (int h = 8; h >= 1; h >>= 1)   // o = 4 h: lanes L and L + o live in slots k and k + h
+#pragma unroll
+    for (int k = 0; k < h; ++k) chan_combine_sym(n[k], mean[k], m2[k], n[k + h], mean[k + h], m2[k + h]);
+  part[w][0][ch] = n[0]; part[w][1][ch] = mean[0]; part[w][2][ch] = m2[0];
+  __syncthreads();
+  if (w == 0) {
+    float sc = 0.f, sh = 0.f;
+    if (ch_ok) {
+      float n1 = part[1][0][ch], mean1 = part[1][1][ch], m21 = part[1][2][ch];
+      chan_combine_sym(n[0], mean[0], m2[0], part[2][0][ch], part[2][1][ch], part[2][2][ch]);   // o = 2: lanes 0 + 2, 1 + 3
+      chan_combine_sym(n1, mean1, m21, part[3][0][ch], part[3][1][ch], part[3][2][ch]);
+      chan_combine_sym(n[0], mean[0], m2[0], n1, mean1, m21);                                    // o = 1
+      float rstd;
+      bn_channel_finish(mean[0], m2[0], M, cc, gamma, beta, eps, momentum, rmean, rvar, sc, sh, rstd, blockIdx.x == 0, scale, shift,
+                        mean_out, rstd_out);
+    }
+    coef[0][ch] = sc; coef[1][ch] = sh;
+  }
+  __syncthreads();
+  if (!col_ok) return;
+  float sc[VE], sh[VE];
+#pragma unroll
+  for (int e = 0; e < VE; ++e) { sc[e] = coef[0][cv * VE + e]; sh[e] = coef[1][cv * VE + e]; }
+  auto emit = [&](long long rr_, float* v, const float* rr) {
+#pragma unroll
+    for (int e = 0; e < VE; ++e) v[e] = v[e] * sc[e] + sh[e];
+    if (res) {
+#pragma unroll
+      for (int e = 0; e < VE; ++e) v[e] += rr[e];
+    }
+#pragma unroll
+    for (int e = 0; e < VE; ++e) v[e] = apply_act(v[e], act);
+    VecT<T>::store(y + rr_ * ldy + c, v);
+  };
+  if (have0) emit(r, v0, q0);
+  for (r += RPT; r < r1; r += RPT) {
+    float v[VE], rr[VE];
+    VecT<T>::load(x + r * ldx + c, v);
+    if (res) VecT<T>::load(res + r * ldr + c, rr);
+    emit(r, v, rr);
+  }
+}
+
+// Backward (the data-gradient launch left per-tile (sum g, sum g * zhat) pairs): wave w holds the tile lanes tl = 4 k + w (k = 0..3) of
+// every channel of the slice.  Every workgroup takes the sums from the partials alone; the row-block-0 workgroup adds them to the
+// affine-gradient buffers, which are zero on entry on every call path (so `0 + s` there is the `s` used here).
+template <typename T>
+__global__ __launch_bounds__(256) void bn_tiles_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ z,
+                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ partials,
+                                                                 int tiles, float inv_m, float* sum_g, float* sum_gz, T* __restrict__ dz,
+                                                                 long long rows, int C, int rows_per_block, int ld_dy, int ld_z,
+                                                                 int ld_dz) {
+  constexpr int VE = VecT<T>::VE, CVS = BNF_SW / VE, RPT = 256 / CVS;
+  __shared__ float2 red[16][BNF_SW + 1];
+  __shared__ float coef[3][BNF_SW];
+  const int c_base = blockIdx.y * BNF_SW;
+  const int cv = threadIdx.x % CVS, rsub = threadIdx.x / CVS;
+  const int c = c_base + cv * VE;
+  const bool col_ok = c < C;
+  const long long r0 = (long long)blockIdx.x * rows_per_block;
+  long long r1 = r0 + rows_per_block;
+  if (r1 > rows) r1 = rows;
+  long long r = r0 + rsub;
+  float a0v[VE], z0v[VE];
+  const bool have0 = col_ok && r < r1;
+  if (have0) {
+    VecT<T>::load(dy + r * ld_dy + c, a0v);
+    VecT<T>::load(z + r * ld_z + c, z0v);
+  }
+  const int ch = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int cc = c_base + ch;
+  const bool ch_ok = cc < C;
+  float gm = 0.f, rs = 0.f, mu = 0.f;
+  if (w == 0 && ch_ok) { gm = gamma[cc]; rs = rstd[cc]; mu = mean[cc]; }
+  float a0[4], a1[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a0[k] = a1[k] = 0.f;
+  for (int tb = 0; tb < tiles; tb += 64) {   // 4 tiles of each of the 4 lanes per trip: 16 loads in flight per thread
+    float2 q[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int t = tb + 16 * u + 4 * k + w;
+        q[u][k] = (ch_ok && t < tiles) ? *(const float2*)(partials + ((size_t)t * C + cc) * 2) : make_float2(0.f, 0.f);
+      }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int t = tb + 16 * u + 4 * k + w;
+        if (ch_ok && t < tiles) bwd_lane_add(a0[k], a1[k], q[u][k]);
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) red[4 * k + w][ch] = make_float2(a0[k], a1[k]);
+  __syncthreads();
+  if (w == 0) {
+    float ca = 0.f, cb = 0.f, c3 = 0.f;
+    if (ch_ok) {
+      float s0, s1;
+      bwd_sum16<BNF_SW + 1>(red, ch, s0, s1);
+      bn_bwd_coeffs(gm, rs, mu, s0, s1, inv_m, ca, cb, c3);
+      if (blockIdx.x == 0) { sum_g[cc] += s0; sum_gz[cc] += s1; }
+    }
+    coef[0][ch] = ca; coef[1][ch] = cb; coef[2][ch] = c3;
+  }
+  __syncthreads();
+  if (!col_ok) return;
+  float ca[VE], cb[VE], c3[VE];
+#pragma unroll
+  for (int e = 0; e < VE; ++e) { ca[e] = coef[0][cv * VE + e]; cb[e] = coef[1][cv * VE + e]; c3[e] = coef[2][cv * VE + e]; }
+  auto emit = [&](long long rr_, const float* a, const float* zz) {
+    float o[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) o[e] = bn_bwd_dz(ca[e], a[e] * act_grad_from_out(zz[e], CAVP_ACT_NONE), cb[e], zz[e], c3[e]);
+    VecT<T>::store(dz + rr_ * ld_dz + c, o);
+  };
+  if (have0) emit(r, a0v, z0v);
+  for (r += RPT; r < r1; r += RPT) {
+    float a[VE], zz[VE];
+    VecT<T>::load(dy + r * ld_dy + c, a);
+    VecT<T>::load(z + r * ld_z + c, zz);
+    emit(r, a, zz);
+  }
+}
+
+// tiles limit of the fused route; 0 switches it off.  196 = the largest size class in which the one launch beat the two on
+// MI355X (the backward; profiles/bn_combine_in_apply.md).  Never above 1023: launches with >= 1024 tiles combine in another
+// order (bn_finalize_tiles_wide_kernel).
+inline int bn_fused_tiles_limit() {
+  static const int limit = std::min(cavp_knob_int("CAVP_BN_FUSED_TILES", 196), 1023);
+  return limit;
+}
+// rows per workgroup of the channel-sliced fused kernels: about 512 workgroups per launch, whole trips of `rpt` rows, >= 64 rows
+inline int bn_fused_rows_per_block(long long rows, int gy, int rpt) {
+  long long gx = std::max(1, 512 / gy);
+  long long rpb = std::max<long long>((rows + gx - 1) / gx, 64);
+  return (int)((rpb + rpt - 1) / rpt * rpt);
+}
+
+extern "C" int cavp_bn_tiles_scale_shift_act(int32_t dtype, const void* x, const float* tile_stats, int32_t tiles, int32_t rows_per_tile,
+                                             const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                                             float* running_var, float* scale, float* shift, float* mean, float* rstd,
+                                             const void* residual, void* y, int64_t rows, int32_t C, int32_t ldx, int32_t ldr,
+                                             int32_t ldy, int32_t act, void* stream) {
+  if (!x || !y || !tile_stats || !gamma || !beta || !scale || !shift || !mean || !rstd || tiles <= 0 || rows_per_tile <= 0 || rows <= 0 ||
+      C <= 0 || (long long)tiles * rows_per_tile < rows || ldx < C || ldy < C || (residual && ldr < C))
+    return CAVP_ERR_BAD_ARG;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return CAVP_ERR_BAD_ARG;
+  if (!dt_ok(dtype) || tiles > bn_fused_tiles_limit()) return CAVP_ERR_UNSUPPORTED;
+  const int VE = dt_ve(dtype);
+  if (C % VE || ldx % VE || ldy % VE || (residual && ldr % VE)) return CAVP_ERR_UNSUPPORTED;
+  if (!al16(x) || !al16(y) || (residual && !al16(residual)) || ((uintptr_t)tile_stats & 7)) return CAVP_ERR_UNSUPPORTED;
+  const int gy = cdiv_h(C, BNF_SW);
+  const int rpb = bn_fused_rows_per_block(rows, gy, 256 / (BNF_SW / VE));
+  const dim3 grid(cdiv_h(rows, rpb), gy);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bn_tiles_scale_shift_act_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T*)x, tile_stats, tiles, rows_per_tile, rows, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, mean, rstd, (const T*)residual, (T*)y, C, rpb, ldx, ldr, ldy, act); });
+  CHECK_LAUNCH();
+}
+
+extern "C" int cavp_bn_tiles_bwd_apply(int32_t dtype, const void* dy, const void* z, const float* mean, const float* rstd,
+                                       const float* gamma, const float* partials, int32_t tiles, float* sum_g, float* sum_gz,
+                                       int64_t rows, int32_t C, int32_t ld_dy, int32_t ld_z, void* dz, int32_t ld_dz, void* stream) {
+  if (!dy || !z || !mean || !rstd || !gamma || !partials || !sum_g || !sum_gz || !dz || tiles <= 0 || rows <= 0 || C <= 0 || ld_dy < C ||
+      ld_z < C || ld_dz < C)
+    return CAVP_ERR_BAD_ARG;
+  if (!dt_ok(dtype) || tiles > bn_fused_tiles_limit()) return CAVP_ERR_UNSUPPORTED;
+  const int VE = dt_ve(dtype);
+  if (C % VE || ld_dy % VE || ld_z % VE || ld_dz % VE) return CAVP_ERR_UNSUPPORTED;
+  if (!al16(dy) || !al16(z) || !al16(dz) || ((uintptr_t)partials & 7)) return CAVP_ERR_UNSUPPORTED;
+  const float inv_m = (float)(1.0 / (double)rows);
+  const int gy = cdiv_h(C, BNF_SW);
+  const int rpb = bn_fused_rows_per_block(rows, gy, 256 / (BNF_SW / VE));
+  const dim3 grid(cdiv_h(rows, rpb), gy);
+  cavp_dispatch_dtype(dtype, [&](auto t) { using T = decltype(t);
+    bn_tiles_bwd_apply_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T*)dy, (const T*)z, mean, rstd, gamma, partials, tiles, inv_m, sum_g, sum_gz, (T*)dz, rows, C, rpb, ld_dy, ld_z, ld_dz); });
   CHECK_LAUNCH();
 }
 

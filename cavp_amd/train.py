@@ -285,6 +285,14 @@ _GROUP_WGRAD = True
 _BRANCH_STREAM = True    # False (tests / A-B only): the down-sample branch of a bottleneck on the main stream (rounds 1-4)
 _SIDE_PACKS = True       # False (A/B only): the audio encoder's weight re-packs on the main stream with all the others (rounds 1-4)
 _FUSE_BN_BWD = True      # False (tests / A-B only): BatchNorm backward always as reduce launch + apply launch (rounds 1-4)
+# The BatchNorm apply passes of launches with few tiles combine the per-tile statistics / partial sums themselves (one launch instead
+# of combine + apply, bit-identical).  False (tests / A-B only): always the two launches.  The two tile limits are where the one
+# launch won per launch on MI355X (profiles/bn_combine_in_apply.md): the backward up to 196 tiles; the forward, whose combine is a
+# chain of divisions every workgroup repeats, only for the single-tile launch of the ASPP pooled branch.  The library declines
+# above its own limit (train_ops.BN_FUSED_TILES) whatever is passed down.
+_BN_COMBINE_IN_APPLY = True
+_BN_COMBINE_FWD_TILES = 1
+_BN_COMBINE_BWD_TILES = 196
 _BN_BWD_READ_Y = False   # True (tests / A-B only): the BatchNorm backward always re-reads y instead of re-deriving the mask from z
 _FUSE_STEM_POOL = True   # False (tests / A-B only): stem bn1 + ReLU and the max pool as two launches with the activation in memory (rounds 1-5)
 
@@ -692,6 +700,7 @@ class TrainPass:
         mom = bn.momentum if bn.momentum is not None else 0.1
         sync = isinstance(bn, nn.SyncBatchNorm) and collectives_on()   # (a forced single-rank group runs the collectives too)
         frozen = (not bn.training) and bn.running_mean is not None   # torch: eval-mode BatchNorm normalises with the running statistics
+        fused_tiles = None
         if frozen:
             # fine-tuning with frozen statistics: y = gamma (z - running_mean) rstd + beta, no update of the running buffers;
             # backward dz = gamma rstd g, dgamma = sum g zhat, dbeta = sum g (no batch-mean terms)
@@ -707,9 +716,14 @@ class TrainPass:
             # ASPP pooled branch
             ts, tiles, rpt = z.tile_stats if z.tile_stats is not None else T.col_tile_stats(z.t)
             count = rows
-            T.bn_finalize_tiles(ts, tiles, rpt, rows, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
-                                bn.running_mean if track else None, bn.running_var if track else None, scale, shift,
-                                mean, rstd)
+            if _BN_COMBINE_IN_APPLY and pool is None and tiles <= _BN_COMBINE_FWD_TILES:
+                # few tiles: the apply launch below combines them for its own channel slices
+                fused_tiles = (ts, tiles, rpt, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
+                               bn.running_mean if track else None, bn.running_var if track else None, mean, rstd)
+            else:
+                T.bn_finalize_tiles(ts, tiles, rpt, rows, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
+                                    bn.running_mean if track else None, bn.running_var if track else None, scale, shift,
+                                    mean, rstd)
         else:
             # SyncBatchNorm (main_vpo_mono.py:130): this rank's (mean, M2) -> ONE all-gather -> Chan combine over the ranks (the
             # same kernel that combines tiles; every rank holds `rows` samples).  Round 1 issued three all-reduces per layer.
@@ -735,7 +749,11 @@ class TrainPass:
             ops.maxpool(z.t, y.t, pk, ps, pp, argmax=am, scale=scale, shift=shift, act=act)
         else:
             y = out if out is not None else V(self.empty(z.t.shape, z.t.dtype))
-            T.scale_shift_act(z.t, scale, shift, y.t, act, residual=residual.t if residual is not None else None)
+            if fused_tiles is not None:
+                T.scale_shift_act(z.t, scale, shift, y.t, act, residual=residual.t if residual is not None else None,
+                                  bn_tiles=fused_tiles)
+            else:
+                T.scale_shift_act(z.t, scale, shift, y.t, act, residual=residual.t if residual is not None else None)
 
         self._use(residual)
         # (ReLU only: its mask is idempotent, so the fallback - a later contribution drops the partial sums and the separate reduce / apply
@@ -759,8 +777,13 @@ class TrainPass:
                 part, tiles = y.bnb_part
                 dz = self.empty(z.t.shape, z.t.dtype)
                 sums = (self.grad_buffer(bn.bias), self.grad_buffer(bn.weight)) if direct else self.zeros_f32(2, c)
-                T.bn_bwd_sum_tiles(part, tiles, sums[0], sums[1])
-                T.bn_act_bwd_apply(dy, None, z.t, mean, rstd, bn.weight.detach(), sums[0], sums[1], ACT_NONE, dz)
+                if _BN_COMBINE_IN_APPLY and tiles <= _BN_COMBINE_BWD_TILES:
+                    # (`sums` is zero here on both paths: a gradient buffer on its first touch of the step, or fresh zeroed scratch)
+                    T.bn_act_bwd_apply(dy, None, z.t, mean, rstd, bn.weight.detach(), sums[0], sums[1], ACT_NONE, dz,
+                                       tile_partials=(part, tiles))
+                else:
+                    T.bn_bwd_sum_tiles(part, tiles, sums[0], sums[1])
+                    T.bn_act_bwd_apply(dy, None, z.t, mean, rstd, bn.weight.detach(), sums[0], sums[1], ACT_NONE, dz)
                 z.set_g(dz)
                 if residual is not None and residual.needs_grad:
                     self.acc_add(residual, dy)

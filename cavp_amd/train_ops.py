@@ -309,8 +309,13 @@ def bn_tiles_to_moments(tile_stats, tiles: int, rows_per_tile: int, count: int, 
            "cavp_bn_tiles_to_moments")
 
 
-def bn_finalize_tiles(tile_stats, tiles: int, rows_per_tile: int, count: int, gamma, beta, eps: float, momentum: float,
-                      running_mean, running_var, scale, shift, mean, rstd) -> None:
+# The library's tile limit of the one-launch BatchNorm routes below (the default of its CAVP_BN_FUSED_TILES knob): above it
+# cavp_bn_tiles_scale_shift_act / cavp_bn_tiles_bwd_apply decline and the wrappers run the two launches.
+BN_FUSED_TILES = 196
+
+
+def _bn_finalize_tiles(tile_stats, tiles: int, rows_per_tile: int, count: int, gamma, beta, eps: float, momentum: float,
+                       running_mean, running_var, scale, shift, mean, rstd) -> None:
     _need_gpu(tile_stats, gamma, beta, scale, shift, mean, rstd)
     _check(_lib.load().cavp_bn_finalize_tiles(_ptr(tile_stats), tiles, rows_per_tile, count, _ptr(gamma), _ptr(beta),
                                               C.c_float(eps), C.c_float(momentum), _ptr(running_mean), _ptr(running_var),
@@ -318,7 +323,17 @@ def bn_finalize_tiles(tile_stats, tiles: int, rows_per_tile: int, count: int, ga
            "cavp_bn_finalize_tiles")
 
 
-def scale_shift_act(x, scale, shift, y, act: int, residual=None) -> torch.Tensor:
+def bn_finalize_tiles(tile_stats, tiles: int, rows_per_tile: int, count: int, gamma, beta, eps: float, momentum: float,
+                      running_mean, running_var, scale, shift, mean, rstd) -> None:
+    _bn_finalize_tiles(tile_stats, tiles, rows_per_tile, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift,
+                       mean, rstd)
+
+
+def scale_shift_act(x, scale, shift, y, act: int, residual=None, bn_tiles=None) -> torch.Tensor:
+    """bn_tiles = (tile_stats, tiles, rows_per_tile, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd): scale and
+    shift are OUTPUTS as well - the launch combines the tile statistics itself (cavp_bn_tiles_scale_shift_act, count = the rows of
+    x) and writes what bn_finalize_tiles would have written, bit for bit.  Where the library declines (too many tiles, layout)
+    the two launches run instead."""
     rows, c, ldx = _rows(x)
     r2, c2, ldy = _rows(y)
     ldr = 0
@@ -327,15 +342,32 @@ def scale_shift_act(x, scale, shift, y, act: int, residual=None) -> torch.Tensor
     _need_gpu(x, y, scale, shift, residual)
     if (rows, c) != (r2, c2) or y.dtype != x.dtype:
         raise _lib.CavpError("scale_shift_act: shape mismatch")
+    if bn_tiles is not None:
+        ts, tiles, rpt, gamma, beta, eps, momentum, rmean, rvar, mean, rstd = bn_tiles
+        _need_gpu(ts, gamma, beta, mean, rstd)
+        if scale is None or shift is None or gamma.numel() != c:
+            raise _lib.CavpError("scale_shift_act(bn_tiles=...): scale / shift outputs of C elements required")
+        st = _lib.load().cavp_bn_tiles_scale_shift_act(dtype_code(x.dtype), _ptr(x), _ptr(ts), tiles, rpt, _ptr(gamma), _ptr(beta),
+                                                       C.c_float(eps), C.c_float(momentum), _ptr(rmean), _ptr(rvar), _ptr(scale),
+                                                       _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(residual), _ptr(y), rows, c, ldx,
+                                                       ldr, ldy, act, _s())
+        if st != _lib.ERR_UNSUPPORTED:
+            _check(st, "cavp_bn_tiles_scale_shift_act")
+            return y
+        _bn_finalize_tiles(ts, tiles, rpt, rows, gamma, beta, eps, momentum, rmean, rvar, scale, shift, mean, rstd)
     _check(_lib.load().cavp_scale_shift_act(dtype_code(x.dtype), _ptr(x), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y),
                                             rows, c, ldx, ldr, ldy, act, _s()), "cavp_scale_shift_act")
     return y
 
 
-def bn_bwd_sum_tiles(partials, tiles: int, sum_g, sum_gz) -> None:
-    """sum_g / sum_gz (f32 [C]) += the per-tile pairs of a conv2d_dgrad(bnb=...) launch, summed over the tiles."""
+def _bn_bwd_sum_tiles(partials, tiles: int, sum_g, sum_gz) -> None:
     _need_gpu(partials, sum_g, sum_gz)
     _check(_lib.load().cavp_bn_bwd_sum_tiles(_ptr(partials), tiles, sum_g.numel(), _ptr(sum_g), _ptr(sum_gz), _s()), "cavp_bn_bwd_sum_tiles")
+
+
+def bn_bwd_sum_tiles(partials, tiles: int, sum_g, sum_gz) -> None:
+    """sum_g / sum_gz (f32 [C]) += the per-tile pairs of a conv2d_dgrad(bnb=...) launch, summed over the tiles."""
+    _bn_bwd_sum_tiles(partials, tiles, sum_g, sum_gz)
 
 
 def bn_act_bwd_reduce(dy, y, z, mean, rstd, act: int, sum_g, sum_gz, fwd_scale=None, fwd_shift=None) -> None:
@@ -352,14 +384,29 @@ def bn_act_bwd_reduce(dy, y, z, mean, rstd, act: int, sum_g, sum_gz, fwd_scale=N
 
 
 def bn_act_bwd_apply(dy, y, z, mean, rstd, gamma, sum_g, sum_gz, act: int, dz, g_out=None, fwd_scale=None,
-                     fwd_shift=None, acc=None) -> torch.Tensor:
-    """acc = (dbeta, dgamma): the two sums are also ADDED to these affine-gradient buffers (sums that arrive in scratch memory)."""
+                     fwd_shift=None, acc=None, tile_partials=None) -> torch.Tensor:
+    """acc = (dbeta, dgamma): the two sums are also ADDED to these affine-gradient buffers (sums that arrive in scratch memory).
+    tile_partials = (partials, tiles) of a conv2d_dgrad(bnb=...) launch (y None, ACT_NONE, no g_out, no acc): the launch sums the
+    partials itself (cavp_bn_tiles_bwd_apply) and ADDS the sums to sum_g / sum_gz, which must be ZERO on entry; bit-identical to
+    bn_bwd_sum_tiles + this apply, which run instead where the library declines (too many tiles, layout)."""
     rows, c, ld_dy = _rows(dy)
     ld_y = _rows(y)[2] if y is not None else 0
     _, _, ld_z = _rows(z)
     _, _, ld_dz = _rows(dz)
     ld_g = _rows(g_out)[2] if g_out is not None else 0
     _need_gpu(dy, y, z, dz, g_out)
+    if tile_partials is not None:
+        part, tiles = tile_partials
+        _need_gpu(part, mean, rstd, gamma, sum_g, sum_gz)
+        if y is not None or g_out is not None or acc is not None or act != 0 or sum_g.numel() != c or sum_gz.numel() != c:
+            raise _lib.CavpError("bn_act_bwd_apply(tile_partials=...): masked gradient only (y None, ACT_NONE, no g_out, no acc)")
+        st = _lib.load().cavp_bn_tiles_bwd_apply(dtype_code(dy.dtype), _ptr(dy), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                                 _ptr(part), tiles, _ptr(sum_g), _ptr(sum_gz), rows, c, ld_dy, ld_z, _ptr(dz), ld_dz,
+                                                 _s())
+        if st != _lib.ERR_UNSUPPORTED:
+            _check(st, "cavp_bn_tiles_bwd_apply")
+            return dz
+        _bn_bwd_sum_tiles(part, tiles, sum_g, sum_gz)
     _check(_lib.load().cavp_bn_act_bwd_apply_acc(dtype_code(dy.dtype), _ptr(dy), _ptr(y), _ptr(z), _ptr(mean), _ptr(rstd),
                                                  _ptr(gamma), _ptr(sum_g), _ptr(sum_gz), rows, c, ld_dy, ld_y, ld_z, act, _ptr(dz),
                                                  ld_dz, _ptr(g_out), ld_g, _ptr(fwd_scale), _ptr(fwd_shift),

@@ -327,6 +327,22 @@ int cavp_bn_act_bwd_apply(int32_t dtype, const void* dy, const void* y, const vo
                           const float* rstd, const float* gamma, const float* sum_g, const float* sum_gz, int64_t rows,
                           int32_t C, int32_t ld_dy, int32_t ld_y, int32_t ld_z, int32_t act, void* dz, int32_t ld_dz,
                           void* g_out, int32_t ld_g, const float* fwd_scale, const float* fwd_shift, void* stream);
+/* Tile combine inside the apply pass, for launches with few tiles (added to ABI 16).
+ *   cavp_bn_tiles_scale_shift_act = cavp_bn_finalize_tiles(count = rows) + cavp_scale_shift_act in ONE launch: every workgroup
+ *     combines the [tiles][C][2] (mean, M2) table for its own 64-channel slice; one workgroup per slice writes scale, shift,
+ *     mean, rstd and updates the running statistics.
+ *   cavp_bn_tiles_bwd_apply = cavp_bn_bwd_sum_tiles + cavp_bn_act_bwd_apply(y = NULL, act = CAVP_ACT_NONE, no g_out) in ONE launch:
+ *     dz is computed from the partials alone and the sums are ADDED to sum_g / sum_gz, which must be zero on entry.
+ * Both give bit-identical results to the two launches they replace.  CAVP_ERR_UNSUPPORTED (nothing launched: use the two
+ * launches) when tiles exceeds the fused limit, when C or a leading dimension is not a multiple of the 16-byte vector, when a
+ * tensor is not 16-byte aligned, or for an unhandled dtype. */
+int cavp_bn_tiles_scale_shift_act(int32_t dtype, const void* x, const float* tile_stats, int32_t tiles, int32_t rows_per_tile,
+                                  const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                                  float* running_var, float* scale, float* shift, float* mean, float* rstd, const void* residual,
+                                  void* y, int64_t rows, int32_t C, int32_t ldx, int32_t ldr, int32_t ldy, int32_t act, void* stream);
+int cavp_bn_tiles_bwd_apply(int32_t dtype, const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
+                            const float* partials, int32_t tiles, float* sum_g, float* sum_gz, int64_t rows, int32_t C,
+                            int32_t ld_dy, int32_t ld_z, void* dz, int32_t ld_dz, void* stream);
 /* dx = dy * act'(.): ReLU / LeakyReLU from the activation OUTPUT, GELU from the pre-activation (ref). */
 int cavp_act_bwd(int32_t dtype, const void* dy, const void* ref, void* dx, int64_t rows, int32_t C, int32_t ld_dy,
                  int32_t ld_ref, int32_t ld_dx, int32_t act, void* stream);
