@@ -7,20 +7,10 @@ import torch
 
 from cavp_amd import ops
 from cavp_amd import train_ops as T
+from tests._attn_ref import rank1_ref as _reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _reference(x, k, v, wq, wp, bp, heads, scale, reps):
-    xb, t, c = x.shape
-    b, d = k.shape[0], c // heads
-    xr = x.repeat(reps, 1, 1)                                     # cavp_model.py:181: torch.cat((fea_v, fea_v.clone()))
-    q = (xr @ wq.t()).view(b, t, heads, d)
-    s = (q * k.view(b, 1, heads, d)).sum(-1) * scale              # [B, T, H]: q @ k^T with ONE key
-    g = torch.sigmoid(s)
-    o = (g.unsqueeze(-1) * v.view(b, 1, heads, d)).reshape(b, t, c)
-    return xr + o @ wp.t() + bp, g.permute(0, 2, 1)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])

@@ -531,6 +531,23 @@ def test_training_entry_points_fail_loudly():
     kv = torch.zeros((4, 304), dtype=dt, device=DEV)
     with pytest.raises(CavpError):
         ops.attn_gate(q, kv, kv, torch.empty((4, 8, 304), dtype=dt, device=DEV), torch.empty((4, 4, 8), device=DEV), 4, 0.1)
+    # attention gate: more heads than the kernels' per-head loops cover (kMaxHeads = 8), forward and backward
+    q9 = torch.zeros((2, 8, 72), dtype=dt, device=DEV)
+    kv9 = torch.zeros((2, 72), dtype=dt, device=DEV)
+    a9 = torch.zeros((2, 9, 8), device=DEV)
+    with pytest.raises(CavpError, match="(?i)unsupported"):
+        ops.attn_gate(q9, kv9, kv9, torch.empty_like(q9), a9, 9, 0.1)
+    with pytest.raises(CavpError, match="(?i)unsupported"):
+        T.attn_gate_bwd(q9, q9, kv9, kv9, a9, None, torch.empty_like(q9), torch.zeros((2, 72), device=DEV), torch.zeros((2, 72), device=DEV), 9, 0.1)
+    # one-key collapse: attn1_finish stages B * heads floats per workgroup in LDS and refuses more than 8192
+    kb = torch.zeros((2049, 8), dtype=dt, device=DEV)
+    w8, dw8 = torch.zeros((8, 8), device=DEV), torch.full((8, 8), 3.0, device=DEV)
+    dup = torch.zeros((2049, 4, 8), device=DEV)
+    with pytest.raises(CavpError, match="(?i)unsupported"):
+        T.attn1_finish(w8, w8, kb, kb, dup, dup, dw8, dw8, 4, 0.5)
+    T.attn1_finish(w8, w8, kb[:2048], kb[:2048], dup[:2048], dup[:2048], dw8, dw8, 4, 0.5)      # 8192 is accepted
+    torch.cuda.synchronize()
+    assert bool((dw8 == 3.0).all())
     # auxiliary epilogue tensor: derivative output without GELU, and a periodic residual that is not a multiple of 256 rows
     w = torch.zeros((128, 1, 1, 64), dtype=dt, device=DEV)
     y = torch.empty((2, 16, 16, 128), dtype=dt, device=DEV)
