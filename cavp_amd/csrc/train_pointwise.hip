@@ -531,16 +531,20 @@ __global__ __launch_bounds__(256) void scale_shift_act_flat_kernel(const T* __re
   }
 }
 
-// dz = a_c * g + b_c * z + c_c (see bn_bwd_apply_kernel): the per-channel coefficients and the per-element expression, shared by
-// the apply kernels so that the fused one (bn_tiles_bwd_apply_kernel) rounds exactly as they do
-__device__ __forceinline__ void bn_bwd_coeffs(float gm, float rs, float mu, float sg, float sgz, float inv_m, float& ca, float& cb,
-                                              float& cc) {
+// dz = a_c * g + b_c * (z - mu_c) + c_c (see bn_bwd_apply_kernel): the per-channel coefficients and the per-element expression, shared
+// by the apply kernels so that the fused one (bn_tiles_bwd_apply_kernel) rounds exactly as they do.  The mean is subtracted from z
+// BEFORE the multiplication: with -b_c * mu_c folded into c_c, b_c * z and c_c cancel where |mu| >> sigma (figures: DESIGN.md 3b);
+// the launches are HBM-bound, one more subtraction per element is free.  The fused multiply-add is written out so that the
+// rounding points do not depend on how the compiler contracts the expression.
+__device__ __forceinline__ void bn_bwd_coeffs(float gm, float rs, float sg, float sgz, float inv_m, float& ca, float& cb, float& cc) {
   const float a = gm * rs;
   ca = a;
   cb = -a * rs * sgz * inv_m;
-  cc = -a * sg * inv_m - cb * mu;
+  cc = -a * sg * inv_m;
 }
-__device__ __forceinline__ float bn_bwd_dz(float ca, float g, float cb, float z, float cc) { return ca * g + cb * z + cc; }
+__device__ __forceinline__ float bn_bwd_dz(float ca, float g, float cb, float z, float mu, float cc) {
+  return __builtin_fmaf(cb, z - mu, ca * g) + cc;
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const T* __restrict__ dy, const T* __restrict__ y,
@@ -558,16 +562,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const T* __restr
   const int c = cv * VE;
   // per-channel coefficients with 16-byte loads (C % VE == 0 and 16-byte aligned vectors: flat_ok): the first version issued
   // 7 x VE scalar loads per thread in front of a row loop of only four trips
-  float ca[VE], cb[VE], cc[VE];
+  float ca[VE], cb[VE], cc[VE], mu[VE];
   {
-    float rs[VE], gm[VE], sg[VE], sgz[VE], mu[VE];
+    float rs[VE], gm[VE], sg[VE], sgz[VE];
 #pragma unroll
     for (int q = 0; q < VE; q += 4) {
       VecT<float>::load(rstd + c + q, rs + q); VecT<float>::load(gamma + c + q, gm + q); VecT<float>::load(sum_g + c + q, sg + q);
       VecT<float>::load(sum_gz + c + q, sgz + q); VecT<float>::load(mean + c + q, mu + q);
     }
 #pragma unroll
-    for (int e = 0; e < VE; ++e) bn_bwd_coeffs(gm[e], rs[e], mu[e], sg[e], sgz[e], inv_m, ca[e], cb[e], cc[e]);
+    for (int e = 0; e < VE; ++e) bn_bwd_coeffs(gm[e], rs[e], sg[e], sgz[e], inv_m, ca[e], cb[e], cc[e]);
     // the sums ARE the affine gradients (dbeta = sum g, dgamma = sum g * zhat): when they arrive in scratch (summed by the
     // data-gradient launch's epilogue, cavp_conv2d_nhwc_bnbwd) one thread per channel vector adds them to the parameter gradients
     if (acc_g && blockIdx.x == 0 && rsub == 0) {
@@ -599,14 +603,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const T* __restr
 #pragma unroll
     for (int e = 0; e < VE; ++e) {
       g[e] = a[e] * act_grad_from_out(yy[e], act);
-      o[e] = bn_bwd_dz(ca[e], g[e], cb[e], zz[e], cc[e]);
+      o[e] = bn_bwd_dz(ca[e], g[e], cb[e], zz[e], mu[e], cc[e]);
     }
     VecT<T>::store(dz + r * ld_dz + c, o);
     if (g_out) VecT<T>::store(g_out + r * ld_g + c, g);
   }
 }
 
-// dz = gamma * rstd * (g - sum_g / M - zhat * sum_gz / M) = a_c * g + b_c * z + c_c,  g = dy * act'(y);
+// dz = gamma * rstd * (g - sum_g / M - zhat * sum_gz / M) = a_c * g + b_c * (z - mu_c) + c_c,  g = dy * act'(y);
 // optionally also writes g (skip-path gradient)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ y,
@@ -622,10 +626,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
   const int c = (blockIdx.y * 16 + cg) * VE;
   if (c >= gm.C) return;
-  float ca[VE], cb[VE], cc[VE];
+  float ca[VE], cb[VE], cc[VE], mu[VE];
 #pragma unroll
   for (int e = 0; e < VE; ++e) {
-    bn_bwd_coeffs(gamma[c + e], rstd[c + e], mean[c + e], sum_g[c + e], sum_gz[c + e], inv_m, ca[e], cb[e], cc[e]);
+    mu[e] = mean[c + e];
+    bn_bwd_coeffs(gamma[c + e], rstd[c + e], sum_g[c + e], sum_gz[c + e], inv_m, ca[e], cb[e], cc[e]);
     if (acc_g && blockIdx.x == 0 && rl == 0) { acc_g[c + e] += sum_g[c + e]; acc_gz[c + e] += sum_gz[c + e]; }   // (see the flat kernel)
   }
   const bool from_z = y == nullptr;   // activation mask re-derived from z (layers without a residual): y is not read
@@ -651,7 +656,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
     for (int e = 0; e < VE; ++e) {
       g[e] = a[e] * act_grad_from_out(yy[e], act);
-      o[e] = bn_bwd_dz(ca[e], g[e], cb[e], zz[e], cc[e]);
+      o[e] = bn_bwd_dz(ca[e], g[e], cb[e], zz[e], mu[e], cc[e]);
     }
     VecT<T>::store(dz + r * ld_dz + c, o);
     if (g_out) VecT<T>::store(g_out + r * ld_g + c, g);
@@ -1913,7 +1918,7 @@ __global__ __launch_bounds__(256) void bn_tiles_bwd_apply_kernel(const T* __rest
                                                                  int ld_dz) {
   constexpr int VE = VecT<T>::VE, CVS = BNF_SW / VE, RPT = 256 / CVS;
   __shared__ float2 red[16][BNF_SW + 1];
-  __shared__ float coef[3][BNF_SW];
+  __shared__ float coef[4][BNF_SW];
   const int c_base = blockIdx.y * BNF_SW;
   const int cv = threadIdx.x % CVS, rsub = threadIdx.x / CVS;
   const int c = c_base + cv * VE;
@@ -1961,20 +1966,20 @@ __global__ __launch_bounds__(256) void bn_tiles_bwd_apply_kernel(const T* __rest
     if (ch_ok) {
       float s0, s1;
       bwd_sum16<BNF_SW + 1>(red, ch, s0, s1);
-      bn_bwd_coeffs(gm, rs, mu, s0, s1, inv_m, ca, cb, c3);
+      bn_bwd_coeffs(gm, rs, s0, s1, inv_m, ca, cb, c3);
       if (blockIdx.x == 0) { sum_g[cc] += s0; sum_gz[cc] += s1; }
     }
-    coef[0][ch] = ca; coef[1][ch] = cb; coef[2][ch] = c3;
+    coef[0][ch] = ca; coef[1][ch] = cb; coef[2][ch] = c3; coef[3][ch] = mu;
   }
   __syncthreads();
   if (!col_ok) return;
-  float ca[VE], cb[VE], c3[VE];
+  float ca[VE], cb[VE], c3[VE], mv[VE];
 #pragma unroll
-  for (int e = 0; e < VE; ++e) { ca[e] = coef[0][cv * VE + e]; cb[e] = coef[1][cv * VE + e]; c3[e] = coef[2][cv * VE + e]; }
+  for (int e = 0; e < VE; ++e) { ca[e] = coef[0][cv * VE + e]; cb[e] = coef[1][cv * VE + e]; c3[e] = coef[2][cv * VE + e]; mv[e] = coef[3][cv * VE + e]; }
   auto emit = [&](long long rr_, const float* a, const float* zz) {
     float o[VE];
 #pragma unroll
-    for (int e = 0; e < VE; ++e) o[e] = bn_bwd_dz(ca[e], a[e] * act_grad_from_out(zz[e], CAVP_ACT_NONE), cb[e], zz[e], c3[e]);
+    for (int e = 0; e < VE; ++e) o[e] = bn_bwd_dz(ca[e], a[e] * act_grad_from_out(zz[e], CAVP_ACT_NONE), cb[e], zz[e], mv[e], c3[e]);
     VecT<T>::store(dz + rr_ * ld_dz + c, o);
   };
   if (have0) emit(r, a0v, z0v);
@@ -2146,6 +2151,8 @@ extern "C" int cavp_colsum(int32_t dtype, const void* x, int64_t rows, int32_t C
 // squares), in the layout the conv epilogue writes (ts[tile][C][2]), for BatchNorm inputs whose producer could not fuse the
 // statistics (split-K convs, the small-Cin stem, channel slices).  Replaces column sum -> mean -> centred column squares (two passes
 // over the tensor, four launches) by one pass + cavp_bn_finalize_tiles; equally cancellation-free.
+// Known limit: the tile sum is plain, so it rounds at the magnitude 128 |mu|; the error of the tile means enters the
+// between-tile term n_a n_b / n (m_b - m_a)^2 of the combine and shows in rstd where |mu| >> sigma.
 template <typename T>
 __global__ __launch_bounds__(256) void col_tile_stats_kernel(const T* __restrict__ x, float* __restrict__ ts, long long rows, int C,
                                                              int ld) {

@@ -12,50 +12,11 @@ import pytest
 import torch
 
 from tests import _attn_ref as R
+from tests._banded import DEV, Banded
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 F32, BF = torch.float32, torch.bfloat16
 DT = pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
-GUARD = 64                                   # elements on either side: 128 / 256 bytes, the payload stays 16-byte aligned
-PAT = {F32: (torch.int32, 0x5A5A5A5A), BF: (torch.int16, 0x5A5A)}
-
-
-class Banded:
-    """Tensors carved out of guard-banded buffers; `check` after the calls."""
-
-    def __init__(self):
-        self.outs = []
-
-    def inp(self, t, dtype):
-        if t is None:
-            return None
-        buf = torch.full((t.numel() + 2 * GUARD,), float("nan"), dtype=dtype, device=DEV)
-        view = buf[GUARD:GUARD + t.numel()].view(t.shape)
-        view.copy_(t.to(dtype))
-        assert view.data_ptr() % 16 == 0 and view.is_contiguous()
-        return view
-
-    def out(self, name, shape, dtype, fill):
-        n = 1
-        for s in shape:
-            n *= s
-        it, pat = PAT[dtype]
-        buf = torch.empty(n + 2 * GUARD, dtype=dtype, device=DEV)
-        buf.view(it).fill_(pat)
-        view = buf[GUARD:GUARD + n].view(shape)
-        view.fill_(fill)
-        assert view.data_ptr() % 16 == 0
-        self.outs.append((name, buf, n, view))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        for name, buf, n, view in self.outs:
-            it, pat = PAT[buf.dtype]
-            ints = buf.view(it)
-            assert bool((ints[:GUARD] == pat).all()) and bool((ints[GUARD + n:] == pat).all()), f"{name}: guard band overwritten"
-            assert bool(torch.isfinite(view).all()), f"{name}: non-finite output"
 
 
 def _cpu(t):

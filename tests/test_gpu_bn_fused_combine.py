@@ -1,5 +1,7 @@
 """BatchNorm tile combine inside the apply pass (cavp_bn_tiles_scale_shift_act / cavp_bn_tiles_bwd_apply) against the two launches it
-replaces, output for output, with torch.equal: the arithmetic and its order are the same, so there is no tolerance.  -m gpu."""
+replaces, output for output, with torch.equal: the arithmetic and its order are the same, so there is no tolerance.  -m gpu.
+(Device against device: the two-launch route these are compared with - and the fused launches themselves - are held to float64 in
+test_gpu_bn_parity.py::test_tile_tables and ::test_launches_of_one_shape.)"""
 import types
 
 import pytest

@@ -608,7 +608,8 @@ def test_fused_bn_backward_statistics_equal_separate_reduce(dtype, streams):
     to summation order (f32) / up to the storage rounding of g (bf16), eagerly and as a graph replay; and the fusion is in use.
     `default_streams`: the product configuration (audio encoder on the side stream, down-sample branches on the branch stream).
     HIP on both sides - a consistency screen of the fused route; the parity anchors of the route are the reference-golden train steps
-    (test_train_step_b8_matches_reference_f32 and friends), which run with it as the default."""
+    (test_train_step_b8_matches_reference_f32 and friends), which run with it as the default.  The separate reduce + apply it is compared
+    with are held to float64 in test_gpu_bn_parity.py::test_launches_of_one_shape, the summed tile pairs in ::test_tile_tables."""
     import cavp_amd.train as TR
     from cavp_amd import train_ops as T
     cfg = dict(C=3, B=8, hw=(96, 96), lds=[False, False, False])
@@ -665,7 +666,8 @@ def test_stem_pool_fused_with_bn_apply_is_bit_identical(dtype):
     the pool compares act(z * scale + shift) rounded to the storage dtype, exactly the values scale_shift_act used to store), the
     un-pooled activation is never written; the backward routes the pooled gradient through the recorded arg-max and is then the same
     BatchNorm + ReLU backward as before.  Deterministic mode: loss and EVERY gradient bit-identical to the two-launch route.
-    (HIP on both sides: a bit-identity screen; the reference-golden train steps run with the fused route as the default.)"""
+    (HIP on both sides: a bit-identity screen; the reference-golden train steps run with the fused route as the default.  The two-launch
+    route's scale_shift_act and BatchNorm + ReLU backward are held to float64 in test_gpu_bn_parity.py::test_launches_of_one_shape.)"""
     import cavp_amd.train as TR
     from cavp_amd import _lib
     cfg = dict(C=3, B=4, hw=(64, 96), lds=[False, False, False])

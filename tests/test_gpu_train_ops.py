@@ -623,8 +623,11 @@ def test_conv_dgrad_fused_bn_backward_stats(case, dt):
     """cavp_conv2d_nhwc_bnbwd: the data-gradient launch that produces the gradient of a BatchNorm + ReLU output stores
     g = (dgrad + residual) * relu'(.) and emits the per-tile sums of cavp_bn_act_bwd_reduce.  Checked against the plain data
     gradient followed by torch on the host: g itself, sum g and sum g * zhat (after cavp_bn_bwd_sum_tiles), and - end to end - the
-    BatchNorm input gradient cavp_bn_act_bwd_apply makes from them against torch.autograd through conv -> BN(train) -> ReLU
-    (resnet.py:75-98)."""
+    BatchNorm input gradient cavp_bn_act_bwd_apply makes from them: against the separate reduce + apply on the plain gradient (device
+    against device), and against the float64 BatchNorm + ReLU backward formula of tests/_bn_ref.py evaluated on exactly what each
+    apply launch read (its gradient tensor, z, mean, rstd, gamma and the two sums), held to the element-wise bars of
+    test_gpu_bn_parity.py (f32 max(4 e32, 1e-6), bf16 3 e_bf16).  The float64 check of the separate route is made where the mask
+    comes from the stored activation; a z-derived mask may flip on the elements whose pre-activation rounds to +-0 (see `bad` below)."""
     ops, T = _mods()
     name, n, h, w, cin, cout, k, s, p, d, with_out = case
     if cin % (8 if dt == torch.bfloat16 else 4):
@@ -692,3 +695,15 @@ def test_conv_dgrad_fused_bn_backward_stats(case, dt):
     T.bn_act_bwd_apply(plain, outv, zv, mean_d, rstd_d, gam.to(DEV), sums_ref[0], sums_ref[1], ops.ACT_RELU, dz_ref, fwd_scale=sc_d, fwd_shift=sh_d)
     T.bn_act_bwd_apply(g, None, zv, mean_d, rstd_d, gam.to(DEV), sums[0], sums[1], ops.ACT_NONE, dz)
     _check(dz, dz_ref.float().cpu(), dt, name + ".dz fused vs separate", 2e-4, 2e-2)
+    # float64: dz = gamma rstd (g - sum g / M - zhat sum g zhat / M) on the tensors each apply launch consumed
+    from tests import _bn_ref as R
+    flat = lambda t: t.float().cpu().reshape(rows, cin)
+    vec = lambda t: t.float().cpu()
+    routes = [("fused", flat(g), sums, dz)]
+    if with_out:
+        routes.append(("separate", flat(plain) * (flat(outv) > 0).float(), sums_ref, dz_ref))
+    for tag, gg, sm, out in routes:
+        ev = lambda model: R.bwd_dz(gg, flat(zv), vec(mean_d), vec(rstd_d), gam.float(), vec(sm[0]), vec(sm[1]), rows, R.ve(dt), model)
+        r = R.elem_ratio(flat(out), ev(None), ev("f32" if dt == torch.float32 else "bf16"), dt)
+        print(f"RATIO bn_act_bwd_apply {'f32' if dt == torch.float32 else 'bf16'} dgrad-{name}-{tag} dz {r:.4f}")
+        assert r <= 1.0, (name, tag, r)
