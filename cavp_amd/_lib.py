@@ -188,6 +188,11 @@ PROTOTYPES = {
     # ---- ResNet-18 audio encoder: fused stem + pool, global max (added to ABI 16) ----
     "cavp_audio_stem_pool": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cavp_global_maxpool_nhwc": (_i32, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    # ---- its training: raw stem conv with tile statistics, global max with winner and backward (added to ABI 16) ----
+    "cavp_audio_stem_train_layout": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "cavp_audio_stem_train": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "cavp_global_maxpool_arg_nhwc": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "cavp_global_maxpool_bwd_nhwc": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     # ---- validation metrics ----
     "cavp_seg_confusion_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _vp]),
     "cavp_mask_iou_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _vp]),

@@ -479,12 +479,31 @@ class CAVP(nn.Module):
         return isinstance(self.audio_backbone.backbone, ResNet18Audio)
 
     def _fence_audio18(self, what: str) -> None:
-        """The ResNet-18 audio encoder has the eval forward only: every training entry point calls this first - before a kernel is
-        queued, before the gradient arena exists or is zeroed - so parameters and BatchNorm buffers are as they were.  (Called as
+        """The ResNet-18 audio encoder trains only after use_audio18_training(): every training entry point calls this first - before a
+        kernel is queued, before the gradient arena exists or is zeroed - so parameters and BatchNorm buffers are as they were.  (Called as
         CAVP._fence_audio18(self, ...) where the entry point's own argument checks are reachable without a model: an object with no
         audio encoder has nothing to fence.)"""
-        if isinstance(getattr(getattr(self, "audio_backbone", None), "backbone", None), ResNet18Audio):
+        if not isinstance(getattr(getattr(self, "audio_backbone", None), "backbone", None), ResNet18Audio):
+            return
+        if not self.__dict__.get("_audio18_train", False):
             raise CavpError(f"CAVP.{what}: {_AUDIO18_TRAINING} (audio_backbone='18')")
+        # switched on (use_audio18_training).  Still fenced, and still before anything is launched: synchronised statistics inside
+        # the encoder - its BatchNorm layers run on the side stream, where the order of collectives across ranks would depend on
+        # stream timing
+        from .train import collectives_on
+        if collectives_on() and any(isinstance(mm, nn.SyncBatchNorm) for mm in self.audio_backbone.modules()):
+            raise CavpError(f"CAVP.{what}: SyncBatchNorm inside the ResNet-18 audio encoder is not supported while collectives are on "
+                            f"(keep its BatchNorm layers local: convert_sync_batchnorm on the other sub-modules only)")
+
+    def use_audio18_training(self, on: bool = True) -> "CAVP":
+        """Opt-in: training of the ResNet-18 audio encoder (audio_backbone='18') - train_step, capture_train_step, forward_train with
+        gradients or batch-statistics BatchNorm, forward_audio on a tape and enable_graphed_autograd run it on the training tape
+        (cavp_amd/train.py::_audio18_stage) instead of raising.  use_audio18_training(False) restores the fence.  A model with the
+        VGGish encoder has nothing to switch: CavpError."""
+        if not self._audio18():
+            raise CavpError("use_audio18_training: this model's audio encoder is not the ResNet-18 one (audio_backbone='18')")
+        self.__dict__["_audio18_train"] = bool(on)   # not a module attribute: it stays out of the state_dict
+        return self
 
     def _pack_audio18(self, P):
         rn = self.audio_backbone.backbone

@@ -255,6 +255,20 @@ def global_maxpool(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def global_maxpool_arg(x: torch.Tensor, out: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
+    """global_maxpool with its winner: arg int32 [N, C] = the first position h * W + w of the maximum (nn.AdaptiveMaxPool2d's rule)."""
+    _need_gpu(x, out, arg)
+    n, h, w, c, ld = _nhwc(x)
+    if out.dtype != x.dtype or tuple(out.shape) != (n, c) or not out.is_contiguous():
+        raise _lib.CavpError("global_maxpool_arg: out must be contiguous [N, C] of the input's dtype")
+    if arg.dtype != torch.int32 or tuple(arg.shape) != (n, c) or not arg.is_contiguous():
+        raise _lib.CavpError("global_maxpool_arg: arg must be contiguous int32 [N, C]")
+    st = _lib.load().cavp_global_maxpool_arg_nhwc(dtype_code(x.dtype), _ptr(x), _ptr(out), _ptr(arg), n, h * w, c, ld,
+                                                  C.c_void_p(_stream()))
+    _lib.check(st, "cavp_global_maxpool_arg_nhwc")
+    return out
+
+
 def audio_stem_pool(x_nchw: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
                     out: torch.Tensor) -> torch.Tensor:
     """ResNet-18 audio stem in one launch: conv 7x7 / 2 / 3 (no bias) -> * scale + shift (folded BatchNorm) -> ReLU -> max pool 3 / 2 / 1.

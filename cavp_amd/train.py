@@ -294,6 +294,9 @@ _BN_COMBINE_IN_APPLY = True
 _BN_COMBINE_FWD_TILES = 1
 _BN_COMBINE_BWD_TILES = 196
 _BN_BWD_READ_Y = False   # True (tests / A-B only): the BatchNorm backward always re-reads y instead of re-deriving the mask from z
+# False (tests / A-B only): the ResNet-18 audio stem of the training pass as the two launches the fused one replaces (conv_smallcin_kxk,
+# then col_tile_stats over the map it wrote)
+_FUSE_AUDIO_STEM = True
 _FUSE_STEM_POOL = True   # False (tests / A-B only): stem bn1 + ReLU and the max pool as two launches with the activation in memory (rounds 1-5)
 
 
@@ -687,6 +690,24 @@ class TrainPass:
         self.tape.append(bwd)
         return y
 
+    def audio_stem(self, x_nchw: torch.Tensor, key: str) -> V:
+        """conv1 of the ResNet-18 audio encoder (7 x 7, stride 2, pad 3, no bias; f32 NCHW input with 1 or 2 channels, no input
+        gradient), raw, with the BatchNorm tile statistics of its output from the same launch (train_ops.audio_stem_train)."""
+        p = self.P[key]
+        n, _, h, w = x_nchw.shape
+        y = V(self.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, p.cout)))
+        # (a bn1 in eval() normalises with its running statistics and never reads this table: the launch still takes it - a few
+        # microseconds of reductions - so that there is one stem launch, not a second variant without them)
+        y.tile_stats = T.audio_stem_train(x_nchw, p.w, y.t, fused=_FUSE_AUDIO_STEM)
+
+        def bwd():
+            if y.g is None:
+                return
+            g = y.g if y.g.is_contiguous() else self._dense_copy(y.g)
+            T.conv_smallcin_kxk_wgrad(x_nchw, g, self.grad_buffer(p.weight), p.kh, p.stride, p.pad)
+        self.tape.append(bwd)
+        return y
+
     def bn_act(self, z: V, bn, act: int, residual: Optional[V] = None, out: Optional[V] = None,
                pool: Optional[Tuple[int, int, int]] = None) -> V:
         """y = act(BN_train(z) + residual); `out` may be a channel slice of a concat buffer.
@@ -854,6 +875,24 @@ class TrainPass:
                 return
             dx = self.empty(x.t.shape, x.t.dtype)
             T.maxpool_bwd(am, y.g if y.g.is_contiguous() else self._dense_copy(y.g), dx, k, stride, pad)
+            self.acc_add(x, dx)
+        self.tape.append(bwd)
+        return y
+
+    def gmp(self, x: V) -> V:
+        """nn.AdaptiveMaxPool2d((1, 1)) with its winner recorded (the first maximum in scan order); the backward writes the whole map's
+        gradient in one pass: the pooled gradient at the winner, 0 elsewhere."""
+        self._use(x)
+        n, h, w, c = x.t.shape
+        y = V(self.empty((n, c), x.t.dtype))
+        am = torch.empty((n, c), dtype=torch.int32, device=self.dev)
+        ops.global_maxpool_arg(x.t, y.t, am)
+
+        def bwd():
+            if y.g is None:
+                return
+            dx = self.empty(x.t.shape, x.t.dtype)
+            T.global_maxpool_bwd(am, y.g if y.g.is_contiguous() else self._dense_copy(y.g), dx)
             self.acc_add(x, dx)
         self.tape.append(bwd)
         return y
@@ -1167,7 +1206,48 @@ def _pack_head(tp: TrainPass, m) -> None:
     tp.pack("cls", up.classifier, pad_cout_to=8)
 
 
+def _pack_audio18(tp: TrainPass, rn) -> None:
+    tp.pack("a18.stem", rn.conv1, raw=True)   # f32 OIHW, as cavp_audio_stem_train reads it
+    for li in range(4):
+        for bi, blk in enumerate(getattr(rn, f"layer{li + 1}")):
+            key = f"a18.l{li + 1}.{bi}"
+            tp.pack(key + ".c1", blk.conv1)
+            tp.pack(key + ".c2", blk.conv2)
+            if blk.downsample is not None:
+                tp.pack(key + ".ds", blk.downsample[0])
+    tp.pack("a18.fc", rn.fc)
+
+
+def _audio18_stage(tp: TrainPass, rn, audio: torch.Tensor) -> V:
+    """The ResNet-18 audio encoder (audio_network.py:18-25; torchvision ResNet._forward_impl) on the tape: [N, in_plane, T, F] f32 ->
+    features [N, latent], no activation behind fc.  BatchNorm as TrainPass.bn_act has it: batch statistics (running statistics and
+    counters updated) for a module in training mode, frozen statistics with gradients for one in eval mode."""
+    if audio.dim() != 4 or audio.shape[1] != rn.in_plane:
+        raise CavpError(f"ResNet-18 audio encoder was built with in_plane={rn.in_plane}: expected [N, {rn.in_plane}, T, F] log-mel "
+                        f"input, got {tuple(audio.shape)}")
+    if audio.dtype != torch.float32:
+        raise CavpError("audio must be float32 (it is converted on the fly by the stem kernel)")
+    z = tp.audio_stem(audio, "a18.stem")
+    x = tp.bn_act(z, rn.bn1, ACT_RELU, pool=(3, 2, 1))
+    for li in range(4):
+        for bi, blk in enumerate(getattr(rn, f"layer{li + 1}")):
+            key = f"a18.l{li + 1}.{bi}"
+            o = tp.bn_act(tp.conv(x, key + ".c1", stats=blk.bn1), blk.bn1, ACT_RELU)
+            if blk.downsample is not None:
+                res = tp.bn_act(tp.conv(x, key + ".ds", stats=blk.downsample[1]), blk.downsample[1], ACT_NONE)
+            else:
+                res = x
+            x = tp.bn_act(tp.conv(o, key + ".c2", stats=blk.bn2), blk.bn2, ACT_RELU, residual=res)
+        tp.named[f"a18.layer{li + 1}"] = x
+    p = tp.gmp(x)
+    tp.named["a18.pool"] = p
+    return tp.conv(p, "a18.fc")
+
+
 def _pack_audio(tp: TrainPass, m) -> None:
+    from .cavp_model import ResNet18Audio
+    if isinstance(m.audio_backbone.backbone, ResNet18Audio):
+        return _pack_audio18(tp, m.audio_backbone.backbone)
     vgg = m.audio_backbone.backbone
     convs = [mm for mm in vgg.features if isinstance(mm, nn.Conv2d)]
     tp.pack("a.conv0", convs[0], raw=True)
@@ -1191,8 +1271,10 @@ def _pack_fusion(tp: TrainPass, m) -> None:
 
 
 def _audio_stage(tp: TrainPass, audio: torch.Tensor) -> V:
-    """VGGish (vgg.py:17-36) on the tape: [N, 1, 96, 64] f32 -> features [N, latent]."""
-    from .cavp_model import VGG
+    """VGGish (vgg.py:17-36) on the tape: [N, 1, 96, 64] f32 -> features [N, latent].  (A ResNet18Audio encoder: _audio18_stage.)"""
+    from .cavp_model import VGG, ResNet18Audio
+    if isinstance(tp.m.audio_backbone.backbone, ResNet18Audio):
+        return _audio18_stage(tp, tp.m.audio_backbone.backbone, audio)
     a = tp.conv_smallcin(audio, "a.conv0", 1, ACT_RELU)
     ci = 1
     for v in VGG.CFG[1:]:
@@ -1412,7 +1494,7 @@ def run_train_forward(model, image: torch.Tensor, audio: torch.Tensor, tp: Train
     lo = _head_stage(tp, m, fusion)
     tp.named.update(fea_v=fea_v, f4=f4, f1=f1, fea_a=fea_a, asp=asp, cat=cat, zcat=zcat)
     if tp._nbt:
-        bump_counters(model, tp._nbt)   # 61 counters, one launch
+        bump_counters(model, tp._nbt)   # one launch: the visual path's 61 counters (+ the 20 of a ResNet-18 audio encoder)
         tp._nbt = []
     if tp.syncbn_poison is not None:   # ranks with unequal shapes in this step (_syncbn_shape_exchange): NaN logits -> NaN loss and gradients
         lo.t.add_(tp.syncbn_poison.to(lo.t.dtype))

@@ -665,6 +665,45 @@ def conv_smallcin_kxk_wgrad(x_nchw, dy, dw_oihw, ks: int, stride: int, pad: int)
     dw_oihw.view(cout, k).add_(tmp.view(cout, kpad)[:, :k])     # 9408 values: gradient accumulation, not compute
 
 
+def audio_stem_train(x_nchw, w_oihw, z, fused: bool = True):
+    """ResNet-18 audio stem for the training pass: z (dense NHWC [N, Hs, Ws, 64], f32 or bf16) = conv 7x7 / 2 / 3 of x (f32 NCHW, 1 or
+    2 channels) with w (f32 OIHW), raw, and the BatchNorm tile statistics of z - returns (tile_stats f32 [tiles, 64, 2], tiles,
+    rows_per_tile).  One launch (cavp_audio_stem_train); where the library declines the shape, or with fused=False (tests / A-B), the
+    two launches it replaces: ops.conv_smallcin_kxk + col_tile_stats."""
+    _need_gpu(x_nchw, w_oihw, z)
+    if x_nchw.dim() != 4 or x_nchw.dtype != torch.float32 or w_oihw.dtype != torch.float32 or not x_nchw.is_contiguous() \
+            or not w_oihw.is_contiguous():
+        raise _lib.CavpError("audio_stem_train: x and w must be contiguous f32 (NCHW / OIHW)")
+    n, cin, h, w = x_nchw.shape
+    if cin not in (1, 2) or tuple(w_oihw.shape) != (64, cin, 7, 7):
+        raise _lib.CavpError(f"audio_stem_train: 1 or 2 input channels and a [64, Cin, 7, 7] weight; got x {tuple(x_nchw.shape)}, "
+                             f"w {tuple(w_oihw.shape)}")
+    if tuple(z.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 64) or not z.is_contiguous():
+        raise _lib.CavpError("audio_stem_train: z must be a dense NHWC [N, Hs, Ws, 64] tensor")
+    lib = _lib.load()
+    tiles, rpt = C.c_int32(0), C.c_int32(0)
+    if fused and lib.cavp_audio_stem_train_layout(n, cin, h, w, C.byref(tiles), C.byref(rpt)):
+        ts = torch.empty((tiles.value, 64, 2), dtype=torch.float32, device=z.device)
+        st = lib.cavp_audio_stem_train(dtype_code(z.dtype), _ptr(x_nchw), _ptr(w_oihw), _ptr(z), _ptr(ts), n, cin, h, w, _s())
+        if st != _lib.ERR_UNSUPPORTED:
+            _check(st, "cavp_audio_stem_train")
+            return ts, tiles.value, rpt.value
+    ops.conv_smallcin_kxk(x_nchw, w_oihw, None, z, 7, 2, 3)
+    return col_tile_stats(z)
+
+
+def global_maxpool_bwd(arg, dy, dx) -> torch.Tensor:
+    """dx [N, H, W, C] (dense, every element written) = dy [N, C] at the winner ops.global_maxpool_arg recorded, 0 elsewhere."""
+    _need_gpu(arg, dy, dx)
+    n, h, w, c, ld = _nhwc(dx)
+    if ld != c or not dx.is_contiguous() or tuple(dy.shape) != (n, c) or dy.dtype != dx.dtype or not dy.is_contiguous() \
+            or arg.dtype != torch.int32 or tuple(arg.shape) != (n, c) or not arg.is_contiguous():
+        raise _lib.CavpError("global_maxpool_bwd: dense dx [N, H, W, C], dy [N, C] of its dtype and int32 arg [N, C] required")
+    _check(_lib.load().cavp_global_maxpool_bwd_nhwc(dtype_code(dx.dtype), _ptr(arg), _ptr(dy), _ptr(dx), n, h * w, c, _s()),
+           "cavp_global_maxpool_bwd_nhwc")
+    return dx
+
+
 def space_to_depth(src, dst, b: int, h: int, w: int, c: int, s: int, inverse: bool = False):
     """[B,H,W,C] -> [B,H/s,W/s,s*s*C] (inverse: back).  Both tensors dense."""
     _need_gpu(src, dst)

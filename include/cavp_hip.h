@@ -782,6 +782,26 @@ int cavp_audio_stem_pool(int32_t dtype, const float* x_nchw, const float* w_oihw
 /* x.amax over HW for NHWC x [N][HW][C] with row stride ldx; y [N][C] of the SAME dtype (a maximum needs no wider type), dense.  HW >= 1;
  * the running maximum starts at -inf.  N <= 65535. */
 int cavp_global_maxpool_nhwc(int32_t dtype, const void* x, void* y, int32_t N, int32_t HW, int32_t C, int32_t ldx, void* stream);
+/* ---- training of that encoder (four entry points added to ABI 16; nothing else changed) ----
+ * conv1 alone, raw, with the BatchNorm tile statistics of its output in ONE launch: z dense NHWC [N][Hs][Ws][64] of dtype (f32
+ * accumulation), 16-byte aligned, and tile_stats f32 [tiles][64][2] = (mean, M2 about that mean) of the values AS STORED in z over
+ * tile t's rows [t * rows_per_tile, min((t + 1) * rows_per_tile, N * Hs * Ws)) of z viewed as [N * Hs * Ws][64] - the table
+ * cavp_bn_finalize_tiles and cavp_bn_tiles_scale_shift_act consume.  cavp_audio_stem_train_layout gives tiles and rows_per_tile
+ * (a band of k stem rows of the flattened N * Hs row index: rows_per_tile = k * Ws) and returns 1, or returns 0 where the launch does
+ * not cover the shape (Cin not 1 or 2, Ws > 192, more than 2^31 - 1 output pixels): cavp_audio_stem_train then returns
+ * CAVP_ERR_UNSUPPORTED and the caller runs cavp_conv_smallcin_kxk_nchw + cavp_col_tile_stats.  One workgroup owns a tile: no
+ * atomics, bit-reproducible. */
+int cavp_audio_stem_train_layout(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t* tiles, int32_t* rows_per_tile);
+int cavp_audio_stem_train(int32_t dtype, const float* x_nchw, const float* w_oihw, void* z_nhwc, float* tile_stats, int32_t N,
+                          int32_t Cin, int32_t H, int32_t W, void* stream);
+/* AdaptiveMaxPool2d((1, 1)) with its winner: y [N][C] (x's dtype) and arg int32 [N][C] = the FIRST position i in [0, HW) (scan order
+ * h * W + w) at which x[n][i][c] equals the maximum - torch's rule, also for NaN: a NaN input gives y = NaN and arg = the LAST NaN's
+ * position.  x NHWC [N][HW][C] with row stride ldx.  N <= 65535. */
+int cavp_global_maxpool_arg_nhwc(int32_t dtype, const void* x, void* y, int32_t* arg, int32_t N, int32_t HW, int32_t C, int32_t ldx,
+                                 void* stream);
+/* its backward: dx dense [N][HW][C] (dtype), EVERY element written: dx[n][i][c] = arg[n][c] == i ? dy[n][c] : 0.  dy dense [N][C]. */
+int cavp_global_maxpool_bwd_nhwc(int32_t dtype, const int32_t* arg, const void* dy, void* dx, int32_t N, int32_t HW, int32_t C,
+                                 void* stream);
 
 /* ---- validation metrics (ABI 13; utils/eval_utils.py MIoU / ForegroundDetect, utils/avsbench_utils.py mask_iou / Eval_Fmeasure) ----
  * Integer counts only, accumulated with integer atomics: results are independent of arrival order.  The float finalisation stays
